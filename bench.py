@@ -16,7 +16,13 @@ Multi-GPU (torchrun, one process per GPU): every rank evaluates its own
 additionally times the RCCL gather of the radiance buffer to rank 0 (reported
 separately; never part of `value`).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the K headline steps and prints the result line.
+`--full` adds everything else the line can carry: the all-cold roofline figure, the PMC /
+profile figures, the parity blocks against the oracle, the secondary lines, configs[4] and
+the CPU baseline.  `--dump-outputs DIR` writes the radiance of the last timed step as
+DIR/<name>.npy (a fixed sample of it above DUMP_MAX_DIRS directions).
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
 """
 import argparse
 import ctypes
@@ -44,6 +50,25 @@ NB = 4                    # rotating headline input batches (4 x 201 MB > the 25
 BYTES_RGB = 24            # 12 B wi + 12 B RGB per direction
 BYTES_SPEC_PER_DIR = 12 + 11 * 4
 BYTES_SAMPLE = 52
+
+
+DUMP_MAX_DIRS = 1 << 20   # --dump-outputs: directions kept per output (3 x 12 B x 1M = 38 MB in all)
+DUMP_SEED = 20260
+
+
+def dump_outputs(dirname, outs, suffix=""):
+    """--dump-outputs: the (3, n) RGB radiance planes the timed steps wrote, one file per
+    turbidity (radiance_T2.npy, ...), fp32.  Above DUMP_MAX_DIRS directions a fixed, seeded
+    sample of the columns (the same for every output and every run), in ascending order."""
+    os.makedirs(dirname, exist_ok=True)
+    n = outs[0].shape[1]
+    idx = None
+    if n > DUMP_MAX_DIRS:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_DIRS, replace=False))
+        idx = torch.from_numpy(pick).to(outs[0].device)
+    for t, out in zip(TURBIDITIES, outs):
+        a = (out if idx is None else out[:, idx]).cpu().numpy()
+        np.save(os.path.join(dirname, f"radiance_T{t:g}{suffix}.npy"), a)
 
 
 def sun_dict(turb, eta_deg=45.0, albedo=0.1, phi=0.0):
@@ -958,13 +983,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--n", type=int, default=N_DIRS, help="directions per GPU")
     ap.add_argument("--precision", default=os.environ.get("SUNSKY_BENCH_PRECISION", "fast"))
-    ap.add_argument("--no-secondary", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--gather", action="store_true", help="also time an RCCL gather of the radiance to rank 0")
-    ap.add_argument("--no-pmc", action="store_true", help="do not read the committed PMC traffic summary")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else the line can carry: all-cold roofline, PMC / "
+                         "profile figures, parity blocks, secondary lines, configs[4], CPU baseline (the --no-* "
+                         "options and --gather select among these)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the radiance of the last timed step to DIR/radiance_T<turbidity>.npy (fp32; a fixed "
+                         "seeded sample of the directions when there are more than DUMP_MAX_DIRS)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary lines")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--gather", action="store_true",
+                    help="with --full: also time an RCCL gather of the radiance to rank 0")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: do not read the committed PMC traffic summary")
     ap.add_argument("--no-c5", action="store_true",
-                    help="skip configs[4] (spectral 11-lambda eval of --c5-dirs per GPU + gather to rank 0, "
-                         "with its parity block; on by default at every N)")
+                    help="with --full: skip configs[4] (spectral 11-lambda eval of --c5-dirs per GPU + gather to "
+                         "rank 0, with its parity block; on by default at every N)")
     ap.add_argument("--headline-only", action="store_true",
                     help="run the settle, warmup and timed headline steps only (for a rocprof trace of the burst)")
     ap.add_argument("--c5-dirs", type=int, default=1 << 26, help="configs[4] directions per GPU (default 64M)")
@@ -974,11 +1007,15 @@ def main():
                     help="meet the other ranks over gloo as the bench does, all-reduce the ranks, print JSON and "
                          "exit before any GPU call (tests)")
     args = ap.parse_args()
+    if args.gather and not args.full:
+        ap.error("--gather needs --full")
     SUN_SLACK[0] = 4.0 if args.precision == "reference" else 1.25
 
     plan = launch_plan(args.gpus, os.environ)
     if plan == "spawn":            # no launcher: start the N ranks, touch no GPU here
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
+    if args.steps < 1:             # in the ranks (the spawning parent only forwards its arguments), before any GPU call
+        raise SystemExit("bench.py: --steps must be at least 1 (the number of timed steps)")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.launch_check:
         print(json.dumps({"plan": plan, "gpus": args.gpus, "world": world, "rank": int(os.environ.get("RANK", "0")),
@@ -1073,12 +1110,39 @@ def main():
     kernel_ms = timer.mean_ms()
     evals_per_step = len(TURBIDITIES) * n
     value = evals_per_step * world * args.steps / elapsed
+    if args.dump_outputs:      # what the last timed step left in `outs`, before anything else writes there
+        dump_outputs(args.dump_outputs, outs, suffix=f"_rank{rank}" if world > 1 else "")
     if args.headline_only:     # the timed burst alone (rocprofv3 --kernel-trace --stats of exactly it)
         if rank == 0:
             print(json.dumps({"metric": "headline burst only", "value": value, "ms_per_step": elapsed / args.steps * 1e3,
                               "kernel_ms": kernel_ms, "steps": args.steps, "warmup": args.warmup}), flush=True)
         if world > 1:
             dist.destroy_process_group()
+        return
+
+    result = None
+    if rank == 0:
+        achieved = BYTES_RGB * n / (kernel_ms * 1e-3) / 1e9
+        kname = "sunsky_eval_rgb_v4_" + ("ref" if args.precision == "reference" else "fast")
+        result = {
+            "metric": "sky-radiance evals/sec (ray-dir \u00d7 \u03bb) at 1/2/4/8 GPU; max-abs \u0394 vs scalar ref", "value": value, "unit": "evals/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "RGB eval(): 16,777,216 uniform upper-hemisphere dirs per GPU x turbidity {2,6,10}",
+                       "dirs_per_gpu": n, "turbidity": list(TURBIDITIES), "sun_elevation_deg": 45,
+                       "albedo": 0.1, "precision": args.precision, "parallelism": f"shard{world}",
+                       **({"rehearsal": f"{world} ranks on {ndev} GPU(s), gloo" +
+                           (", C5 gather through the RCCL test double" if double else "")} if rehearsal else {})},
+            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": achieved / HBM_PEAK_GBS,
+                         "kernel": kname,
+                         "kernel_ms": kernel_ms, "bytes_per_launch": BYTES_RGB * n},
+        }
+    if not args.full:          # a plain run: the headline line alone
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        teardown(world, rank, None, False)
         return
 
     # Headline kernel with every launch's inputs from HBM: the NB batches evaluated
@@ -1103,40 +1167,22 @@ def main():
     step(0)
     torch.cuda.synchronize()
 
-    result = None
     if rank == 0:
-        achieved = BYTES_RGB * n / (kernel_ms * 1e-3) / 1e9
-        kname = "sunsky_eval_rgb_v4_" + ("ref" if args.precision == "reference" else "fast")
         traffic, traffic_src = (None, None) if args.no_pmc else pmc_traffic(kname)
-        parity = parity_check(ems, wi, outs)
-        result = {
-            "metric": "sky-radiance evals/sec (ray-dir \u00d7 \u03bb) at 1/2/4/8 GPU; max-abs \u0394 vs scalar ref", "value": value, "unit": "evals/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "RGB eval(): 16,777,216 uniform upper-hemisphere dirs per GPU x turbidity {2,6,10}",
-                       "dirs_per_gpu": n, "turbidity": list(TURBIDITIES), "sun_elevation_deg": 45,
-                       "albedo": 0.1, "precision": args.precision, "parallelism": f"shard{world}",
-                       **({"rehearsal": f"{world} ranks on {ndev} GPU(s), gloo" +
-                           (", C5 gather through the RCCL test double" if double else "")} if rehearsal else {})},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS,
-                         "achieved_all_cold": BYTES_RGB * n / (cold_ms * 1e-3) / 1e9,
-                         "frac_all_cold": BYTES_RGB * n / (cold_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "kernel_ms_all_cold": cold_ms,
-                         "cache_note": f"the timed steps rotate over {NB} distinct 201 MB input batches (805 MB > "
-                                       "the 256 MiB Infinity Cache): launch 1 of a step reads its directions from "
-                                       "HBM, launches 2 and 3 (the next turbidities of the same batch) may find "
-                                       "them in the Infinity Cache, as the workload re-reads them.  *_all_cold "
-                                       "evaluates the batches round-robin so every launch reads from HBM.  PMC "
-                                       "FETCH_SIZE counts Infinity-Cache hits too (MI355X_MICROARCH.md 'HBM'), so "
-                                       "`traffic` is bytes past the L2, not HBM-only bytes",
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": kname,
-                         "kernel_ms": kernel_ms, "bytes_per_launch": BYTES_RGB * n,
-                         "profile": burst_profile(kname)},
-            "parity": parity,
-        }
+        result["roofline"].update({
+            "achieved_all_cold": BYTES_RGB * n / (cold_ms * 1e-3) / 1e9,
+            "frac_all_cold": BYTES_RGB * n / (cold_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            "kernel_ms_all_cold": cold_ms,
+            "cache_note": f"the timed steps rotate over {NB} distinct 201 MB input batches (805 MB > "
+                          "the 256 MiB Infinity Cache): launch 1 of a step reads its directions from "
+                          "HBM, launches 2 and 3 (the next turbidities of the same batch) may find "
+                          "them in the Infinity Cache, as the workload re-reads them.  *_all_cold "
+                          "evaluates the batches round-robin so every launch reads from HBM.  PMC "
+                          "FETCH_SIZE counts Infinity-Cache hits too, so "
+                          "`traffic` is bytes past the L2, not HBM-only bytes",
+            "traffic": traffic, "traffic_source": traffic_src,
+            "profile": burst_profile(kname)})
+        result["parity"] = parity_check(ems, wi, outs)
 
     # ---------------------------------------------------------------- secondary
     if not args.no_secondary:

@@ -210,6 +210,35 @@ def test_sigterm_to_the_spawning_parent_ends_every_rank():
             raise AssertionError(f"rank pid {pid} outlived the parent")
 
 
+def test_dump_outputs_writes_a_fixed_sample(tmp_path):
+    """--dump-outputs: one fp32 (3, m) file per turbidity; above DUMP_MAX_DIRS directions the same
+    seeded, ascending sample of the columns in every file and every run, under 64 MB in all; a
+    smaller output whole."""
+    import torch
+    bench = _bench()
+    n = bench.DUMP_MAX_DIRS + 1000
+    outs = [torch.arange(3 * n, dtype=torch.float32).reshape(3, n) + k for k in range(3)]   # exact in fp32
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outs)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) == ["radiance_T10.npy", "radiance_T2.npy", "radiance_T6.npy"]
+    total = 0
+    for k, t in enumerate(("2", "6", "10")):
+        a, b = (np.load(tmp_path / d / f"radiance_T{t}.npy") for d in ("a", "b"))
+        assert a.dtype == np.float32 and a.shape == (3, bench.DUMP_MAX_DIRS)
+        np.testing.assert_array_equal(a, b)
+        idx = a[0] - k                                   # row 0 of output k holds column index + k
+        assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < n
+        np.testing.assert_array_equal(a[2], idx + 2 * n + k)
+        if k:
+            np.testing.assert_array_equal(idx, first)
+        first = idx
+        total += a.nbytes
+    assert total <= 64e6
+    bench.dump_outputs(str(tmp_path / "c"), [o[:, :1000] for o in outs], suffix="_rank1")
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "radiance_T6_rank1.npy"), outs[1][:, :1000].numpy())
+
+
 def test_secondary_bursts_span_the_timed_window():
     """Round 5: each secondary burst runs at least SECONDARY_TIMED_MS of launches (the shader clock
     drifts over tens of ms under sustained load), never fewer than the step-derived count."""

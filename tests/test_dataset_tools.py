@@ -12,8 +12,12 @@ import sunsky_amd as ss
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 REF = "/root/reference"
-CSV = os.path.join(REF, "sunsky-testing/res/datasets/model_hosek.csv")
-TGMM_BIN = os.path.join(REF, "resources/sunsky/datasets/tgmm_tables.bin")
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+# fixtures: the reference's sunsky-testing/res/datasets/model_hosek.csv and its shipped
+# resources/sunsky/datasets/*.bin, byte for byte
+CSV = os.path.join(GOLDEN, "model_hosek.csv")
+REF_DATASETS = os.path.join(GOLDEN, "datasets")
+TGMM_BIN = os.path.join(REF_DATASETS, "tgmm_tables.bin")
 
 
 def read_pack_entry(name):
@@ -30,7 +34,6 @@ def read_pack_entry(name):
     raise KeyError(name)
 
 
-@pytest.mark.skipif(not os.path.exists(CSV), reason="reference CSV not present (GPU box)")
 def test_tgmm_table_regenerated_from_csv_is_bit_exact(tmp_path):
     from mk_tgmm_tables import SHAPE, tgmm_from_csv
     table = tgmm_from_csv(CSV)
