@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -21,6 +22,7 @@
 
 #include "sunsky_dataset.h"
 #include "sunsky_errors.h"
+#include "sunsky_kernel_args.h"
 #include "sunsky_model.h"
 #include "sunsky_profiler.h"
 #include "sunsky_props.h"
@@ -106,35 +108,68 @@ void check_xform_form(hipModule_t mod, const std::string& path, bool want_identi
 // ---------------------------------------------------------------- kernels
 // The sampling kernels are instantiated per variant (RGB / spectral) so each
 // carries only its own tables and registers.
-enum KernelId {
-    K_EVAL_RGB_V4, K_EVAL_RGB_V1, K_EVAL_SPEC_BCAST_V4, K_EVAL_SPEC_BCAST_V1, K_EVAL_SPEC_NODES_V4,
-    K_EVAL_SPEC_RAYS_V4, K_EVAL_SPEC_RAYS_V1, K_SAMPLE_DIRECTION_RGB, K_SAMPLE_DIRECTION_SPEC, K_PDF_DIRECTION_V4, K_PDF_DIRECTION_V1, K_SAMPLE_WAVELENGTHS_RGB,
-    K_SAMPLE_WAVELENGTHS_SPEC, K_SAMPLE_RAY_RGB, K_SAMPLE_RAY_SPEC, K_BAKE_RGB, K_BAKE_SPEC,
-    K_DIRECT_DIFFUSE_RGB, K_DIRECT_DIFFUSE_SPEC, K_SAMPLE_DIRECTION_RGB_LEAN, K_SAMPLE_DIRECTION_SPEC_LEAN,
-    K_DIRECT_DIFFUSE_RAYS, K_SAMPLE_DIRECTION_RGB_LEAN_PLAIN, K_DIRECT_CONDUCTOR_RGB, K_DIRECT_CONDUCTOR_SPEC,
-    K_DIRECT_CONDUCTOR_RAYS, K_SAMPLE_DIRECTION_SPEC_LEAN4_SORTED, K_SAMPLE_RAY_RGB_SORTED,
-    K_SAMPLE_DIRECTION_RGB_FULL_SORTED, K_EVAL_SPEC_RAYS4_V4, K_DEBUG_SUN_SEGMENTS, K_SAMPLE_DIRECTION_RGB_POS_SORTED,
-    K_SAMPLE_DIRECTION_SPEC_POS_SORTED, K_COUNT
-};
-const char* kKernelNames[K_COUNT] = {
-    "sunsky_eval_rgb_v4", "sunsky_eval_rgb_v1", "sunsky_eval_spec_bcast_v4", "sunsky_eval_spec_bcast_v1",
-    "sunsky_eval_spec_nodes_v4", "sunsky_eval_spec_rays_v4", "sunsky_eval_spec_rays_v1", "sunsky_sample_direction_rgb",
-    "sunsky_sample_direction_spec", "sunsky_pdf_direction_v4", "sunsky_pdf_direction_v1",
-    "sunsky_sample_wavelengths_rgb",
-    "sunsky_sample_wavelengths_spec", "sunsky_sample_ray_rgb", "sunsky_sample_ray_spec",
-    "sunsky_bake_latlong_rgb", "sunsky_bake_latlong_spec", "sunsky_direct_diffuse_rgb", "sunsky_direct_diffuse_spec",
-    "sunsky_sample_direction_rgb_lean", "sunsky_sample_direction_spec_lean", "sunsky_direct_diffuse_rays",
-    "sunsky_sample_direction_rgb_lean_plain", "sunsky_direct_conductor_rgb", "sunsky_direct_conductor_spec",
-    "sunsky_direct_conductor_rays", "sunsky_sample_direction_spec_lean4_sorted", "sunsky_sample_ray_rgb_sorted",
-    "sunsky_sample_direction_rgb_full_sorted", "sunsky_eval_spec_rays4_v4", "sunsky_debug_sun_segments",
-    "sunsky_sample_direction_rgb_pos_sorted", "sunsky_sample_direction_spec_pos_sorted"};
+//
+// The kernel table, one row per kernel: X(id, name, workgroups per CU, dir, per).
+//  * name: the code objects export name_fast and name_ref.
+//  * workgroups per CU: the cap of the grid-stride launches, sized to fill every CU several
+//    times over (cdna_hip_programming.md Guideline 11).  From the tools/kbench.cpp sweep on
+//    MI355X (profiles/r01_v2_kbench_grid_sweep.log): RGB eval 64 (60.4 us vs 64.9 us at 16
+//    for 16M directions), spectral 64, sampling 64 (profiles/r01_v5_kbench.log,
+//    r01_v7_tune.log); sample_ray 32, from the sweep over 8/16/32/64
+//    (profiles/r03_v18_kbench_grid_ray_wavelengths.log); 16 where no sweep is recorded.
+//  * dir: the eval kernels are instantiated twice: eval(si) negates wi at compile time,
+//    eval_direction(ds) uses ds.d as is (name_dir_fast, name_dir_ref).
+//  * per: samples per work item: 4 consecutive directions per lane in the VEC = 4 kernels
+//    (their batches are multiples of 4); in the wave-sorted kernels one wave takes a window
+//    of 4 (RGB) or 3 (spectral) x 64 samples.
+#define SUNSKY_KERNELS(X)                                                                          \
+    X(EVAL_RGB_V4, "sunsky_eval_rgb_v4", 64, true, 4)                                              \
+    X(EVAL_RGB_V1, "sunsky_eval_rgb_v1", 64, true, 1)                                              \
+    X(EVAL_SPEC_BCAST_V4, "sunsky_eval_spec_bcast_v4", 64, false, 4)                               \
+    X(EVAL_SPEC_BCAST_V1, "sunsky_eval_spec_bcast_v1", 64, false, 1)                               \
+    X(EVAL_SPEC_NODES_V4, "sunsky_eval_spec_nodes_v4", 64, false, 4)                               \
+    X(EVAL_SPEC_RAYS_V4, "sunsky_eval_spec_rays_v4", 64, true, 4)                                  \
+    X(EVAL_SPEC_RAYS_V1, "sunsky_eval_spec_rays_v1", 64, true, 1)                                  \
+    X(EVAL_SPEC_RAYS4_V4, "sunsky_eval_spec_rays4_v4", 64, true, 4)                                \
+    X(PDF_DIRECTION_V4, "sunsky_pdf_direction_v4", 64, false, 4)                                   \
+    X(PDF_DIRECTION_V1, "sunsky_pdf_direction_v1", 64, false, 1)                                   \
+    X(SAMPLE_DIRECTION_RGB, "sunsky_sample_direction_rgb", 64, false, 1)                           \
+    X(SAMPLE_DIRECTION_RGB_LEAN, "sunsky_sample_direction_rgb_lean", 64, false, 4)                 \
+    X(SAMPLE_DIRECTION_RGB_LEAN_PLAIN, "sunsky_sample_direction_rgb_lean_plain", 64, false, 1)     \
+    X(SAMPLE_DIRECTION_RGB_FULL_SORTED, "sunsky_sample_direction_rgb_full_sorted", 64, false, 4)   \
+    X(SAMPLE_DIRECTION_RGB_POS_SORTED, "sunsky_sample_direction_rgb_pos_sorted", 64, false, 4)     \
+    X(SAMPLE_DIRECTION_SPEC, "sunsky_sample_direction_spec", 64, false, 1)                         \
+    X(SAMPLE_DIRECTION_SPEC_LEAN, "sunsky_sample_direction_spec_lean", 64, false, 1)               \
+    X(SAMPLE_DIRECTION_SPEC_LEAN4_SORTED, "sunsky_sample_direction_spec_lean4_sorted", 64, false, 3) \
+    X(SAMPLE_DIRECTION_SPEC_POS_SORTED, "sunsky_sample_direction_spec_pos_sorted", 64, false, 3)   \
+    X(SAMPLE_RAY_RGB, "sunsky_sample_ray_rgb", 32, false, 1)                                       \
+    X(SAMPLE_RAY_RGB_SORTED, "sunsky_sample_ray_rgb_sorted", 64, false, 4)                         \
+    X(SAMPLE_RAY_SPEC, "sunsky_sample_ray_spec", 32, false, 1)                                     \
+    X(SAMPLE_WAVELENGTHS_RGB, "sunsky_sample_wavelengths_rgb", 16, false, 1)                       \
+    X(SAMPLE_WAVELENGTHS_SPEC, "sunsky_sample_wavelengths_spec", 64, false, 1)                     \
+    X(BAKE_RGB, "sunsky_bake_latlong_rgb", 64, false, 1)                                           \
+    X(BAKE_SPEC, "sunsky_bake_latlong_spec", 64, false, 1)                                         \
+    X(DIRECT_DIFFUSE_RGB, "sunsky_direct_diffuse_rgb", 64, false, 1)                               \
+    X(DIRECT_DIFFUSE_SPEC, "sunsky_direct_diffuse_spec", 64, false, 1)                             \
+    X(DIRECT_DIFFUSE_RAYS, "sunsky_direct_diffuse_rays", 64, false, 1)                             \
+    X(DIRECT_CONDUCTOR_RGB, "sunsky_direct_conductor_rgb", 64, false, 1)                           \
+    X(DIRECT_CONDUCTOR_SPEC, "sunsky_direct_conductor_spec", 64, false, 1)                         \
+    X(DIRECT_CONDUCTOR_RAYS, "sunsky_direct_conductor_rays", 64, false, 1)                         \
+    X(DEBUG_SUN_SEGMENTS, "sunsky_debug_sun_segments", 16, false, 1)
 
-// eval kernels instantiated twice: eval(si) negates wi at compile time,
-// eval_direction(ds) uses ds.d as is (the "_dir" kernels)
-bool has_dir_form(KernelId k) {
-    return k == K_EVAL_RGB_V4 || k == K_EVAL_RGB_V1 || k == K_EVAL_SPEC_RAYS_V4 || k == K_EVAL_SPEC_RAYS_V1 ||
-           k == K_EVAL_SPEC_RAYS4_V4;
-}
+#define X(id, name, wg, dir, per) K_##id,
+enum KernelId { SUNSKY_KERNELS(X) K_COUNT };
+#undef X
+struct KernelInfo {
+    const char* name;
+    int blocks_per_cu;
+    bool dir_form;
+    int per_item;
+};
+#define X(id, name, wg, dir, per) {name, wg, dir, per},
+constexpr KernelInfo kKernels[] = {SUNSKY_KERNELS(X)};
+#undef X
+static_assert(sizeof(kKernels) / sizeof(kKernels[0]) == K_COUNT, "one table row per KernelId");
 
 struct DeviceModule {
     hipModule_t module = nullptr, module_ident = nullptr;
@@ -164,27 +199,27 @@ DeviceModule* module_for_device(int dev) {
     check_xform_form(m->module, path, false);
     hip_check(hipModuleLoad(&m->module_ident, ipath.c_str()), "hipModuleLoad(sunsky_kernels_ident.hsaco)");
     check_xform_form(m->module_ident, ipath, true);
+    auto get = [](hipFunction_t* f, hipModule_t mod, const std::string& name) {
+        hip_check(hipModuleGetFunction(f, mod, name.c_str()), name.c_str());
+    };
     for (int id = 0; id < 2; ++id)
         for (int p = 0; p < 2; ++p)
             for (int k = 0; k < K_COUNT; ++k) {
                 hipModule_t mod = id ? m->module_ident : m->module;
-                std::string name = std::string(kKernelNames[k]) + (p == SUNSKY_PRECISION_FAST ? "_fast" : "_ref");
-                hip_check(hipModuleGetFunction(&m->fn[id][p][k], mod, name.c_str()), name.c_str());
-                if (has_dir_form((KernelId)k)) {
-                    std::string dn = std::string(kKernelNames[k]) + (p == SUNSKY_PRECISION_FAST ? "_dir_fast" : "_dir_ref");
-                    hip_check(hipModuleGetFunction(&m->fn_dir[id][p][k], mod, dn.c_str()), dn.c_str());
-                }
+                const std::string name = kKernels[k].name, prec = p == SUNSKY_PRECISION_FAST ? "_fast" : "_ref";
+                get(&m->fn[id][p][k], mod, name + prec);
+                if (kKernels[k].dir_form) get(&m->fn_dir[id][p][k], mod, name + "_dir" + prec);
             }
-    hip_check(hipModuleGetFunction(&m->jvp_rgb, m->module, "sunsky_eval_jvp_rgb"), "sunsky_eval_jvp_rgb");
-    hip_check(hipModuleGetFunction(&m->jvp_spec, m->module, "sunsky_eval_jvp_spec"), "sunsky_eval_jvp_spec");
-    hip_check(hipModuleGetFunction(&m->vjp_rgb, m->module, "sunsky_eval_vjp_rgb"), "sunsky_eval_vjp_rgb");
-    hip_check(hipModuleGetFunction(&m->vjp_spec, m->module, "sunsky_eval_vjp_spec"), "sunsky_eval_vjp_spec");
-    hip_check(hipModuleGetFunction(&m->grad_reduce, m->module, "sunsky_grad_reduce"), "sunsky_grad_reduce");
-    hip_check(hipModuleGetFunction(&m->latlong_tables, m->module, "sunsky_latlong_tables"), "sunsky_latlong_tables");
-    hip_check(hipModuleGetFunction(&m->stage_tangent, m->module, "sunsky_stage_tangent"), "sunsky_stage_tangent");
-    hip_check(hipModuleGetFunction(&m->stage_radiance, m->module, "sunsky_stage_radiance"), "sunsky_stage_radiance");
-    hip_check(hipModuleGetFunction(&m->quad_points, m->module, "sunsky_stage_quad_points"), "sunsky_stage_quad_points");
-    hip_check(hipModuleGetFunction(&m->quad_finish, m->module, "sunsky_stage_quad_finish"), "sunsky_stage_quad_finish");
+    get(&m->jvp_rgb, m->module, "sunsky_eval_jvp_rgb");
+    get(&m->jvp_spec, m->module, "sunsky_eval_jvp_spec");
+    get(&m->vjp_rgb, m->module, "sunsky_eval_vjp_rgb");
+    get(&m->vjp_spec, m->module, "sunsky_eval_vjp_spec");
+    get(&m->grad_reduce, m->module, "sunsky_grad_reduce");
+    get(&m->latlong_tables, m->module, "sunsky_latlong_tables");
+    get(&m->stage_tangent, m->module, "sunsky_stage_tangent");
+    get(&m->stage_radiance, m->module, "sunsky_stage_radiance");
+    get(&m->quad_points, m->module, "sunsky_stage_quad_points");
+    get(&m->quad_finish, m->module, "sunsky_stage_quad_finish");
     hip_check(hipDeviceGetAttribute(&m->cu_count, hipDeviceAttributeMultiprocessorCount, dev),
               "hipDeviceGetAttribute");
     DeviceModule* raw = m.release();
@@ -194,41 +229,15 @@ DeviceModule* module_for_device(int dev) {
 
 constexpr int kBlock = 256;
 
-// Grid-stride launches sized to fill every CU several times over
-// (cdna_hip_programming.md Guideline 11).  Workgroups per CU from the
-// tools/kbench.cpp sweep on MI355X (profiles/r01_v2_kbench_grid_sweep.log):
-// RGB eval 64 (60.4 us vs 64.9 us at 16 for 16M directions), spectral 64,
-// sampling 64 (profiles/r01_v5_kbench.log, r01_v7_tune.log).
-// SUNSKY_AMD_BLOCKS_PER_CU overrides every kernel class.
-int blocks_per_cu(KernelId k) {
+// Grid of a grid-stride launch of kernel k over `work_items`: one thread each, up to the
+// table's workgroups per CU.  SUNSKY_AMD_BLOCKS_PER_CU overrides every kernel's (read once).
+unsigned grid_for(const DeviceModule* m, KernelId k, size_t work_items) {
     static const int env = [] {
         const char* e = std::getenv("SUNSKY_AMD_BLOCKS_PER_CU");
         return e ? std::max(1, std::atoi(e)) : 0;
     }();
-    if (env) return env;
-    switch (k) {
-        case K_EVAL_RGB_V4: case K_EVAL_RGB_V1: return 64;
-        case K_EVAL_SPEC_BCAST_V4: case K_EVAL_SPEC_BCAST_V1: case K_EVAL_SPEC_NODES_V4: return 64;
-        case K_SAMPLE_DIRECTION_RGB: case K_SAMPLE_DIRECTION_SPEC: case K_PDF_DIRECTION_V4: case K_PDF_DIRECTION_V1:
-        case K_SAMPLE_DIRECTION_RGB_LEAN: case K_SAMPLE_DIRECTION_SPEC_LEAN:
-        case K_SAMPLE_DIRECTION_RGB_LEAN_PLAIN: case K_SAMPLE_DIRECTION_SPEC_LEAN4_SORTED:
-        case K_SAMPLE_RAY_RGB_SORTED: case K_SAMPLE_DIRECTION_RGB_FULL_SORTED: case K_SAMPLE_DIRECTION_RGB_POS_SORTED:
-        case K_SAMPLE_DIRECTION_SPEC_POS_SORTED:
-            return 64;
-        case K_BAKE_RGB: case K_BAKE_SPEC: return 64;
-        case K_DIRECT_DIFFUSE_RGB: case K_DIRECT_DIFFUSE_SPEC: case K_DIRECT_DIFFUSE_RAYS: return 64;
-        case K_DIRECT_CONDUCTOR_RGB: case K_DIRECT_CONDUCTOR_SPEC: case K_DIRECT_CONDUCTOR_RAYS: return 64;
-        case K_EVAL_SPEC_RAYS_V4: case K_EVAL_SPEC_RAYS_V1: case K_EVAL_SPEC_RAYS4_V4: return 64;
-        // kbench sweep over 8/16/32/64 (profiles/r03_v18_kbench_grid_ray_wavelengths.log)
-        case K_SAMPLE_RAY_RGB: case K_SAMPLE_RAY_SPEC: return 32;
-        case K_SAMPLE_WAVELENGTHS_SPEC: return 64;
-        default: return 16;
-    }
-}
-
-unsigned grid_for(const DeviceModule* m, KernelId k, size_t work_items) {
     size_t need = (work_items + kBlock - 1) / kBlock;
-    size_t cap = (size_t)m->cu_count * (size_t)blocks_per_cu(k);
+    size_t cap = (size_t)m->cu_count * (size_t)(env ? env : kKernels[k].blocks_per_cu);
     return (unsigned)std::max<size_t>(1, std::min(need, cap));
 }
 
@@ -244,19 +253,23 @@ void launch(hipFunction_t f, unsigned grid, hipStream_t stream, void** args, uns
 // neutral (profiles/r06_v8_nodes_occupancy_cold.log, r06_v7_ab_nodes_lds_cap.log).
 constexpr unsigned kNodesLdsCap = 32000;
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+// The VEC = 4 kernels move 16 bytes per lane and plane (4 mask bytes).  How many of a batch's
+// n samples they can take: the multiple of 4 below n when every plane of `planes` is 16-byte
+// aligned, every plane stride of `strides` a multiple of 4 and the mask 4-byte aligned, else 0.
+size_t vec4_count(size_t n, std::initializer_list<const void*> planes, std::initializer_list<size_t> strides,
+                  const uint8_t* active) {
+    bool vec = n >= 4 && (!active || ((uintptr_t)active & 3u) == 0);
+    for (const void* p : planes) vec = vec && ((uintptr_t)p & 15u) == 0;
+    for (size_t s : strides) vec = vec && (s % 4) == 0;
+    return vec ? (n & ~(size_t)3) : 0;
+}
 
-struct LambdaSet {   // mirrors the kernel-side struct
-    int m;
-    int lo[kMaxBroadcastLambda];
-    float f[kMaxBroadcastLambda];
-};
-
-struct LatLong {     // mirrors the kernel-side struct
-    int w, h;
-    float theta0, dtheta, phi0, dphi;
-    const float* tab;
-};
+// part(offset, count, vec): the VEC = 4 body over [0, n4), then the VEC = 1 tail over [n4, n)
+template <typename F>
+void vec4_then_tail(size_t n, size_t n4, F&& part) {
+    if (n4) part((size_t)0, n4, true);
+    if (n4 < n) part(n4, n - n4, false);
+}
 
 // normalized_wavelengths / floor2int / lerp factor of eval, sunsky.cpp:326-332
 LambdaSet make_lambda_set(const float* lam, int m) {
@@ -292,30 +305,6 @@ struct DeviceScope {
     }
     DeviceScope(const DeviceScope&) = delete;
     DeviceScope& operator=(const DeviceScope&) = delete;
-};
-
-struct StageArgs {   // mirrors the kernel-side struct (sunsky_kernels.hip)
-    SunskyKArgs* state;
-    float* sun_table;
-    const float* sky_params_ds;
-    const float* sky_rad_ds;
-    const float* sun_rad_ds;
-    RadianceStage rs;
-    float albedo[kNbWavelengths];
-    int nch, variant, sun_block;
-    float sky_scale;
-};
-
-constexpr int kQuadBlock = 256;   // sunsky_kernels.hip: one quadrature row per workgroup
-struct QuadArgs {    // mirrors the kernel-side struct (sunsky_kernels.hip)
-    SunskyKArgs* state;
-    const float* qx;
-    const float* qw;
-    float* rows;
-    int nq, nch;
-    float cie_y[kNbWavelengths];
-    float sky_scale, sun_scale;
-    int* status;
 };
 
 }  // namespace
@@ -541,15 +530,10 @@ struct sunsky_emitter {
         hip_check(hipStreamIsCapturing(s, &cs), "hipStreamIsCapturing");
         return cs == hipStreamCaptureStatusNone ? 1 : 0;
     }
-    hipFunction_t fn(KernelId k, hipStream_t s) const {
+    // Batch calls need the emitter's device state: a host-only emitter
+    // (sunsky_emitter_create_host) has none and rejects them.
+    void require_device() const {
         if (!mod) throw std::invalid_argument("host-only emitter (sunsky_emitter_create_host) cannot launch kernels");
-        return mod->fn[xform_form(s)][precision][k];
-    }
-    // eval (sign < 0: wo = -wi) or eval_direction (sign > 0: wo = d) form of an eval kernel
-    hipFunction_t fn_eval(KernelId k, float sign, hipStream_t s) const {
-        if (!mod) throw std::invalid_argument("host-only emitter (sunsky_emitter_create_host) cannot launch kernels");
-        const int x = xform_form(s);
-        return sign < 0.f ? mod->fn[x][precision][k] : mod->fn_dir[x][precision][k];
     }
 
     ~sunsky_emitter() {
@@ -601,11 +585,28 @@ struct sunsky_emitter {
     }
 };
 
-// Batch calls need the emitter's device state: a host-only emitter
-// (sunsky_emitter_create_host) has none and rejects them.
-void require_device(const sunsky_emitter* e) {
-    if (!e->mod) throw std::invalid_argument("host-only emitter (sunsky_emitter_create_host) cannot launch kernels");
-}
+// What a batch entry point launches with: the emitter's device made current for the scope
+// of the call, its device state and the caller's stream.
+struct Launcher {
+    const sunsky_emitter* e;
+    DeviceScope scope;
+    const SunskyKArgs* K;
+    hipStream_t s;
+    Launcher(const sunsky_emitter* em, void* stream)
+        : e(em), scope(em->device), K(em->d_state), s((hipStream_t)stream) {   // a host-only emitter: no device to scope
+        e->require_device();
+    }
+
+    // Kernel k over n samples.  dir: the eval_direction form (wo = d) of an eval kernel.
+    void run(KernelId k, size_t n, void** args, bool dir = false) const {
+        const size_t per = (size_t)kKernels[k].per_item, items = (n + per - 1) / per;
+        const unsigned grid = grid_for(e->mod, k, items);
+        const bool multi_step = items > (size_t)grid * kBlock;
+        const auto& fns = dir ? e->mod->fn_dir : e->mod->fn;
+        launch(fns[e->xform_form(s)][e->precision][k], grid, s, args,
+               k == K_EVAL_SPEC_NODES_V4 && multi_step ? kNodesLdsCap : 0u);
+    }
+};
 
 extern "C" {
 
@@ -732,12 +733,9 @@ int sunsky_emitter_sun_segments(const sunsky_emitter* e, const float* cos_theta,
     if (n == 0) return SUNSKY_OK;
     if (!cos_theta || !pos) return fail(SUNSKY_ERROR_INVALID_VALUE, "null input / output pointer");
     return guarded([&] {
-        require_device(e);
-        DeviceScope dev_scope(e->device);
-        const SunskyKArgs* K = e->d_state;
-        hipStream_t s = (hipStream_t)stream;
-        void* args[] = {&K, &cos_theta, &n, &pos};
-        launch(e->fn(K_DEBUG_SUN_SEGMENTS, s), grid_for(e->mod, K_DEBUG_SUN_SEGMENTS, n), s, args);
+        Launcher lc(e, stream);
+        void* args[] = {&lc.K, &cos_theta, &n, &pos};
+        lc.run(K_DEBUG_SUN_SEGMENTS, n, args);
     });
 }
 
@@ -874,49 +872,30 @@ static int eval_impl(const sunsky_emitter* e, sunsky_vec3_in w, const float* lam
     if (nout > 1 && ostride < n) return fail(SUNSKY_ERROR_INVALID_VALUE, "out_stride < n");
     if (spec && nlam > 1 && lstride < n) return fail(SUNSKY_ERROR_INVALID_VALUE, "wl_stride < n");
     return guarded([&] {
-        require_device(e);
-        hipStream_t s = (hipStream_t)stream;
-        DeviceScope dev_scope(e->device);
-        const SunskyKArgs* K = e->d_state;
+        Launcher lc(e, stream);
+        const bool dir = sign > 0.f;   // eval_direction: wo = d
         if (!spec) {
-            bool vec = n >= 4 && aligned16(w.x) && aligned16(w.y) && aligned16(w.z) && aligned16(out) &&
-                       (ostride % 4) == 0 && (!active || ((uintptr_t)active & 3u) == 0);
-            size_t n4 = vec ? (n & ~(size_t)3) : 0;
-            if (n4) {
-                const float *x = w.x, *y = w.y, *z = w.z;
-                void* args[] = {&K, &x, &y, &z, &active, &n4, &out, &ostride, &sign};
-                launch(e->fn_eval(K_EVAL_RGB_V4, sign, s), grid_for(e->mod, K_EVAL_RGB_V4, n4 / 4), s, args);
-            }
-            if (n4 < n) {
-                const float *x = w.x + n4, *y = w.y + n4, *z = w.z + n4;
-                const uint8_t* a = active ? active + n4 : nullptr;
-                float* o = out + n4;
-                size_t rem = n - n4;
-                void* args[] = {&K, &x, &y, &z, &a, &rem, &o, &ostride, &sign};
-                launch(e->fn_eval(K_EVAL_RGB_V1, sign, s), grid_for(e->mod, K_EVAL_RGB_V1, rem), s, args);
-            }
+            const size_t n4 = vec4_count(n, {w.x, w.y, w.z, out}, {ostride}, active);
+            vec4_then_tail(n, n4, [&](size_t off, size_t cnt, bool vec) {
+                const float *x = w.x + off, *y = w.y + off, *z = w.z + off;
+                const uint8_t* a = active ? active + off : nullptr;
+                float* o = out + off;
+                void* args[] = {&lc.K, &x, &y, &z, &a, &cnt, &o, &ostride, &sign};
+                lc.run(vec ? K_EVAL_RGB_V4 : K_EVAL_RGB_V1, cnt, args, dir);
+            });
         } else {
-            // VEC = 4 over rays when every plane is 16-byte aligned; VEC = 1 tail
-            bool vec = n >= 4 && aligned16(w.x) && aligned16(w.y) && aligned16(w.z) && aligned16(out) &&
-                       aligned16(lam) && (ostride % 4) == 0 && (nlam == 1 || (lstride % 4) == 0) &&
-                       (!active || ((uintptr_t)active & 3u) == 0);
-            size_t n4 = vec ? (n & ~(size_t)3) : 0;
+            // the wavelength planes too; their stride matters only when there is a second plane
+            const size_t n4 = vec4_count(n, {w.x, w.y, w.z, out, lam}, {ostride, nlam == 1 ? 0 : lstride}, active);
             int nl = nlam;
-            if (n4) {
-                const float *x = w.x, *y = w.y, *z = w.z;
-                void* args[] = {&K, &x, &y, &z, &lam, &lstride, &nl, &active, &n4, &out, &ostride, &sign};
+            vec4_then_tail(n, n4, [&](size_t off, size_t cnt, bool vec) {
+                const float *x = w.x + off, *y = w.y + off, *z = w.z + off, *l = lam + off;
+                const uint8_t* a = active ? active + off : nullptr;
+                float* o = out + off;
+                void* args[] = {&lc.K, &x, &y, &z, &l, &lstride, &nl, &a, &cnt, &o, &ostride, &sign};
                 // Mitsuba's Spectrum<Float, 4>: the kernel with the count compiled in
-                const KernelId kr = nlam == 4 ? K_EVAL_SPEC_RAYS4_V4 : K_EVAL_SPEC_RAYS_V4;
-                launch(e->fn_eval(kr, sign, s), grid_for(e->mod, kr, n4 / 4), s, args);
-            }
-            if (n4 < n) {
-                const float *x = w.x + n4, *y = w.y + n4, *z = w.z + n4, *l = lam + n4;
-                const uint8_t* a = active ? active + n4 : nullptr;
-                float* o = out + n4;
-                size_t rem = n - n4;
-                void* args[] = {&K, &x, &y, &z, &l, &lstride, &nl, &a, &rem, &o, &ostride, &sign};
-                launch(e->fn_eval(K_EVAL_SPEC_RAYS_V1, sign, s), grid_for(e->mod, K_EVAL_SPEC_RAYS_V1, rem), s, args);
-            }
+                lc.run(!vec ? K_EVAL_SPEC_RAYS_V1 : nlam == 4 ? K_EVAL_SPEC_RAYS4_V4 : K_EVAL_SPEC_RAYS_V4, cnt, args,
+                       dir);
+            });
         }
     });
 }
@@ -948,30 +927,16 @@ int sunsky_eval_spectral_broadcast(const sunsky_emitter* e, sunsky_vec3_in w, co
     bool nodes = m == kNbWavelengths;
     for (int k = 0; nodes && k < m; ++k) nodes = L.lo[k] == k && L.f[k] == 0.f;
     return guarded([&] {
-        require_device(e);
-        hipStream_t s = (hipStream_t)stream;
-        DeviceScope dev_scope(e->device);
-        const SunskyKArgs* K = e->d_state;
+        Launcher lc(e, stream);
         float sign = -1.f;
-        bool vec = n >= 4 && aligned16(w.x) && aligned16(w.y) && aligned16(w.z) && aligned16(out) &&
-                   (ostride % 4) == 0 && (!active || ((uintptr_t)active & 3u) == 0);
-        size_t n4 = vec ? (n & ~(size_t)3) : 0;
-        if (n4) {
-            const float *x = w.x, *y = w.y, *z = w.z;
-            void* args[] = {&K, &L, &x, &y, &z, &active, &n4, &out, &ostride, &sign};
-            const unsigned grid = grid_for(e->mod, K_EVAL_SPEC_BCAST_V4, n4 / 4);
-            const bool multi_step = n4 / 4 > (size_t)grid * kBlock;
-            launch(e->fn(nodes ? K_EVAL_SPEC_NODES_V4 : K_EVAL_SPEC_BCAST_V4, s), grid, s, args,
-                   nodes && multi_step ? kNodesLdsCap : 0u);
-        }
-        if (n4 < n) {
-            const float *x = w.x + n4, *y = w.y + n4, *z = w.z + n4;
-            const uint8_t* a = active ? active + n4 : nullptr;
-            float* o = out + n4;
-            size_t rem = n - n4;
-            void* args[] = {&K, &L, &x, &y, &z, &a, &rem, &o, &ostride, &sign};
-            launch(e->fn(K_EVAL_SPEC_BCAST_V1, s), grid_for(e->mod, K_EVAL_SPEC_BCAST_V1, rem), s, args);
-        }
+        const size_t n4 = vec4_count(n, {w.x, w.y, w.z, out}, {ostride}, active);
+        vec4_then_tail(n, n4, [&](size_t off, size_t cnt, bool vec) {
+            const float *x = w.x + off, *y = w.y + off, *z = w.z + off;
+            const uint8_t* a = active ? active + off : nullptr;
+            float* o = out + off;
+            void* args[] = {&lc.K, &L, &x, &y, &z, &a, &cnt, &o, &ostride, &sign};
+            lc.run(!vec ? K_EVAL_SPEC_BCAST_V1 : nodes ? K_EVAL_SPEC_NODES_V4 : K_EVAL_SPEC_BCAST_V4, cnt, args);
+        });
     });
 }
 
@@ -993,11 +958,9 @@ int sunsky_sample_direction(const sunsky_emitter* e, const float* ux, const floa
     if ((ds_p.x != nullptr) != (ds_p.y != nullptr) || (ds_p.x != nullptr) != (ds_p.z != nullptr))
         return fail(SUNSKY_ERROR_INVALID_VALUE, "ds_p must be all-NULL or all-set");
     return guarded([&] {
-        require_device(e);
-        DeviceScope dev_scope(e->device);
-        const SunskyKArgs* K = e->d_state;
+        Launcher lc(e, stream);
         int nl = spec ? nlam : 0;
-        void* args[] = {&K, &ux, &uy, (void*)&it_p.x, (void*)&it_p.y, (void*)&it_p.z, &lam, &lstride, &nl, &active, &n,
+        void* args[] = {&lc.K, &ux, &uy, (void*)&it_p.x, (void*)&it_p.y, (void*)&it_p.z, &lam, &lstride, &nl, &active, &n,
                         &ds_d.x, &ds_d.y, &ds_d.z, &ds_pdf, &ds_dist, &ds_p.x, &ds_p.y, &ds_p.z, &weight, &wstride};
         // the common call (no it.p, ds.dist, ds.p or mask) takes the kernel with those
         // paths compiled out: same results, no SGPR spills (sampling)
@@ -1023,12 +986,7 @@ int sunsky_sample_direction(const sunsky_emitter* e, const float* ux, const floa
                                         : sorted_general ? K_SAMPLE_DIRECTION_RGB_FULL_SORTED
                                         : (!active && !unsorted) ? K_SAMPLE_DIRECTION_RGB_POS_SORTED
                                                                  : K_SAMPLE_DIRECTION_RGB);
-        // the wave-sorted kernels: one wave takes a window of 4 (RGB) or 3 (spectral) x 64 samples
-        const size_t items = (k == K_SAMPLE_DIRECTION_RGB_LEAN || k == K_SAMPLE_DIRECTION_RGB_FULL_SORTED ||
-                              k == K_SAMPLE_DIRECTION_RGB_POS_SORTED) ? (n + 3) / 4
-                             : (k == K_SAMPLE_DIRECTION_SPEC_LEAN4_SORTED || k == K_SAMPLE_DIRECTION_SPEC_POS_SORTED)
-                                   ? (n + 2) / 3 : n;
-        launch(e->fn(k, (hipStream_t)stream), grid_for(e->mod, k, items), (hipStream_t)stream, args);
+        lc.run(k, n, args);
     });
 }
 
@@ -1039,25 +997,15 @@ int sunsky_pdf_direction(const sunsky_emitter* e, sunsky_vec3_in d, const uint8_
     if (n == 0) return SUNSKY_OK;
     if (!d.x || !d.y || !d.z || !pdf) return fail(SUNSKY_ERROR_INVALID_VALUE, "null direction / output pointer");
     return guarded([&] {
-        require_device(e);
-        DeviceScope dev_scope(e->device);
-        const SunskyKArgs* K = e->d_state;
-        hipStream_t s = (hipStream_t)stream;
-        bool vec = n >= 4 && aligned16(d.x) && aligned16(d.y) && aligned16(d.z) && aligned16(pdf) &&
-                   (!active || ((uintptr_t)active & 3u) == 0);
-        size_t n4 = vec ? (n & ~(size_t)3) : 0;
-        if (n4) {
-            void* args[] = {&K, (void*)&d.x, (void*)&d.y, (void*)&d.z, &active, &n4, &pdf};
-            launch(e->fn(K_PDF_DIRECTION_V4, s), grid_for(e->mod, K_PDF_DIRECTION_V4, n4 / 4), s, args);
-        }
-        if (n4 < n) {
-            const float *x = d.x + n4, *y = d.y + n4, *z = d.z + n4;
-            const uint8_t* a = active ? active + n4 : nullptr;
-            float* p = pdf + n4;
-            size_t rem = n - n4;
-            void* args[] = {&K, &x, &y, &z, &a, &rem, &p};
-            launch(e->fn(K_PDF_DIRECTION_V1, s), grid_for(e->mod, K_PDF_DIRECTION_V1, rem), s, args);
-        }
+        Launcher lc(e, stream);
+        const size_t n4 = vec4_count(n, {d.x, d.y, d.z, pdf}, {}, active);
+        vec4_then_tail(n, n4, [&](size_t off, size_t cnt, bool vec) {
+            const float *x = d.x + off, *y = d.y + off, *z = d.z + off;
+            const uint8_t* a = active ? active + off : nullptr;
+            float* p = pdf + off;
+            void* args[] = {&lc.K, &x, &y, &z, &a, &cnt, &p};
+            lc.run(vec ? K_PDF_DIRECTION_V4 : K_PDF_DIRECTION_V1, cnt, args);
+        });
     });
 }
 
@@ -1072,10 +1020,8 @@ int sunsky_sample_ray(const sunsky_emitter* e, const float* wls, const float* s2
     if (e->kargs.variant == kSpectral && !wls) return fail(SUNSKY_ERROR_INVALID_VALUE, "null wavelength sample");
     if (lstride < n || wstride < n) return fail(SUNSKY_ERROR_INVALID_VALUE, "stride < n");
     return guarded([&] {
-        require_device(e);
-        DeviceScope dev_scope(e->device);
-        const SunskyKArgs* K = e->d_state;
-        void* args[] = {&K, &wls, &s2x, &s2y, &s3x, &s3y, &active, &n, &o.x, &o.y, &o.z,
+        Launcher lc(e, stream);
+        void* args[] = {&lc.K, &wls, &s2x, &s2y, &s3x, &s3y, &active, &n, &o.x, &o.y, &o.z,
                         &d.x, &d.y, &d.z, &lam, &lstride, &weight, &wstride};
         // RGB without a mask: the wave-sorted kernel (one wave per window of 4 x 64 rays);
         // SUNSKY_AMD_UNSORTED_SAMPLING=1 keeps the unsorted one (A/B, the bitwise test)
@@ -1083,8 +1029,7 @@ int sunsky_sample_ray(const sunsky_emitter* e, const float* wls, const float* s2
         const bool unsorted = uns && uns[0] == '1';
         const KernelId k = e->kargs.variant == kSpectral ? K_SAMPLE_RAY_SPEC
                            : (!active && !unsorted) ? K_SAMPLE_RAY_RGB_SORTED : K_SAMPLE_RAY_RGB;
-        launch(e->fn(k, (hipStream_t)stream), grid_for(e->mod, k, k == K_SAMPLE_RAY_RGB_SORTED ? (n + 3) / 4 : n), (hipStream_t)stream,
-               args);
+        lc.run(k, n, args);
     });
 }
 
@@ -1097,12 +1042,9 @@ int sunsky_sample_wavelengths(const sunsky_emitter* e, sunsky_vec3_in w, const f
     if (e->kargs.variant == kSpectral && !sample) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sample");
     if (lstride < n || wstride < n) return fail(SUNSKY_ERROR_INVALID_VALUE, "stride < n");
     return guarded([&] {
-        require_device(e);
-        DeviceScope dev_scope(e->device);
-        const SunskyKArgs* K = e->d_state;
-        void* args[] = {&K, (void*)&w.x, (void*)&w.y, (void*)&w.z, &sample, &active, &n, &lam, &lstride, &weight, &wstride};
-        const KernelId k = e->kargs.variant == kSpectral ? K_SAMPLE_WAVELENGTHS_SPEC : K_SAMPLE_WAVELENGTHS_RGB;
-        launch(e->fn(k, (hipStream_t)stream), grid_for(e->mod, k, n), (hipStream_t)stream, args);
+        Launcher lc(e, stream);
+        void* args[] = {&lc.K, (void*)&w.x, (void*)&w.y, (void*)&w.z, &sample, &active, &n, &lam, &lstride, &weight, &wstride};
+        lc.run(e->kargs.variant == kSpectral ? K_SAMPLE_WAVELENGTHS_SPEC : K_SAMPLE_WAVELENGTHS_RGB, n, args);
     });
 }
 
@@ -1127,9 +1069,8 @@ int sunsky_eval_jvp(const sunsky_emitter* e, int param, const float* tangent, in
         TangentStage ts;
         if (stage || n == 0) ts = e->model->tangent_stage(param, tangent, tangent_count);   // validates param / count
         if (n == 0) return;
-        require_device(e);
-        hipStream_t st = (hipStream_t)stream;
-        DeviceScope dev_scope(e->device);
+        Launcher lc(e, stream);
+        hipStream_t st = lc.s;
         e->ad_begin(st);   // ordered after the previous AD call (which may read d_jvp), any stream
         if (stage) {   // the tangent tables, staged on the device (sunsky_stage_tangent)
             if (!e->d_jvp) hip_check(hipMalloc(&e->d_jvp, sizeof(float) * sunsky_emitter::kJvpFloats), "hipMalloc");
@@ -1139,17 +1080,16 @@ int sunsky_eval_jvp(const sunsky_emitter* e, int param, const float* tangent, in
             e->jvp_key = key;
             e->jvp_rev = e->rev;
         }
-        const SunskyKArgs* K = e->d_state;
         const float* jvp = e->d_jvp;
         const float *x = wi.x, *y = wi.y, *z = wi.z;
         float sign = -1.f;
         if (!spec) {
-            void* args[] = {&K, &jvp, &x, &y, &z, &active, &n, &out, &d_out, &ostride, &sign};
-            launch(e->mod->jvp_rgb, grid_for(e->mod, K_EVAL_RGB_V1, n), (hipStream_t)stream, args);
+            void* args[] = {&lc.K, &jvp, &x, &y, &z, &active, &n, &out, &d_out, &ostride, &sign};
+            launch(e->mod->jvp_rgb, grid_for(e->mod, K_EVAL_RGB_V1, n), st, args);
         } else {
             int nl = nlam;
-            void* args[] = {&K, &jvp, &x, &y, &z, &lam, &lstride, &nl, &active, &n, &out, &d_out, &ostride, &sign};
-            launch(e->mod->jvp_spec, grid_for(e->mod, K_EVAL_SPEC_RAYS_V1, n), (hipStream_t)stream, args);
+            void* args[] = {&lc.K, &jvp, &x, &y, &z, &lam, &lstride, &nl, &active, &n, &out, &d_out, &ostride, &sign};
+            launch(e->mod->jvp_spec, grid_for(e->mod, K_EVAL_SPEC_RAYS_V1, n), st, args);
         }
         e->ad_end(st);
     });
@@ -1165,7 +1105,7 @@ int sunsky_emitter_tangent_tables(const sunsky_emitter* e, int param, const floa
         static_assert(sunsky_emitter::kJvpFloats == SUNSKY_TANGENT_FLOATS, "tangent buffer layout");
         std::vector<float> v(total, 0.f);
         if (on_device) {
-            require_device(e);
+            e->require_device();
             DeviceScope g(e->device);
             float* d = nullptr;
             hip_check(hipMalloc(&d, sizeof(float) * total), "hipMalloc");
@@ -1200,7 +1140,7 @@ int sunsky_eval_vjp(const sunsky_emitter* e, sunsky_vec3_in wi, const float* lam
     if (nout > 1 && ostride < n) return fail(SUNSKY_ERROR_INVALID_VALUE, "out_stride < n");
     if (spec && nlam > 1 && lstride < n) return fail(SUNSKY_ERROR_INVALID_VALUE, "wl_stride < n");
     return guarded([&] {
-        require_device(e);
+        Launcher lc(e, stream);
         // basis tangents: turbidity, albedo (all channels at once: channel c's tables depend on
         // albedo[c] only, so the all-ones tangent is the diagonal), sun_direction x / y / z
         const SunskyModel& M = *e->model;
@@ -1209,8 +1149,7 @@ int sunsky_eval_vjp(const sunsky_emitter* e, sunsky_vec3_in wi, const float* lam
         // partials, so the one-workgroup reduce below stays short (16384 partials took 0.3 ms)
         const unsigned grid = (unsigned)std::max<size_t>(
             1, std::min<size_t>((n + kBlock - 1) / kBlock, (size_t)e->mod->cu_count * 6));
-        hipStream_t st = (hipStream_t)stream;
-        DeviceScope dev_scope(e->device);
+        hipStream_t st = lc.s;
         const bool stage = !e->d_vjp || e->vjp_rev != e->rev;
         const bool had_ad = e->ad_done != nullptr;
         e->ad_begin(st);   // ordered after the previous AD call (d_vjp / d_partials readers), any stream
@@ -1246,23 +1185,21 @@ int sunsky_eval_vjp(const sunsky_emitter* e, sunsky_vec3_in wi, const float* lam
             e->stage_tangent(A, st);
             e->vjp_rev = e->rev;
         }
-        const SunskyKArgs* K = e->d_state;
         const float* vjp = e->d_vjp;
         float* partials = e->d_partials;
         const float *x = wi.x, *y = wi.y, *z = wi.z;
         float sign = -1.f;
         if (!spec) {
-            void* args[] = {&K, &vjp, &x, &y, &z, &active, &n, &d_out, &ostride, &sign, &partials};
+            void* args[] = {&lc.K, &vjp, &x, &y, &z, &active, &n, &d_out, &ostride, &sign, &partials};
             launch(e->mod->vjp_rgb, grid, st, args);
         } else {
             int nl = nlam;
-            void* args[] = {&K, &vjp, &x, &y, &z, &lam, &lstride, &nl, &active, &n, &d_out, &ostride, &sign, &partials};
+            void* args[] = {&lc.K, &vjp, &x, &y, &z, &lam, &lstride, &nl, &active, &n, &d_out, &ostride, &sign, &partials};
             launch(e->mod->vjp_spec, grid, st, args);
         }
         unsigned nb = grid;
         void* rargs[] = {&partials, &nb, &grad};
-        hip_check(hipModuleLaunchKernel(e->mod->grad_reduce, 1, 1, 1, 256, 1, 1, 0, st, rargs, nullptr),
-                  "hipModuleLaunchKernel");
+        launch(e->mod->grad_reduce, 1, st, rargs);
         e->ad_end(st);
     });
 }
@@ -1284,10 +1221,8 @@ int sunsky_bake_latlong(const sunsky_emitter* e, int width, int height, float th
     LatLong G = {width, height, theta0, height > 1 ? (theta1 - theta0) / (float)(height - 1) : 0.f,
                  phi0, width > 1 ? (phi1 - phi0) / (float)(width - 1) : 0.f, nullptr};
     return guarded([&] {
-        require_device(e);
-        DeviceScope dev_scope(e->device);
-        const SunskyKArgs* K = e->d_state;
-        hipStream_t s = (hipStream_t)stream;
+        Launcher lc(e, stream);
+        hipStream_t s = lc.s;
         const size_t need = 2 * (size_t)width + 2 * (size_t)height;
         // the angle tables are per emitter: order this bake after the previous one (any
         // stream), so a bake on another stream cannot rewrite them under a running kernel
@@ -1310,12 +1245,13 @@ int sunsky_bake_latlong(const sunsky_emitter* e, int width, int height, float th
             launch(e->mod->latlong_tables, tg, s, targs);
         }
         if (!spec) {
-            void* args[] = {&K, &G, &out, &ostride};
-            launch(e->fn(K_BAKE_RGB, s), grid_for(e->mod, K_BAKE_RGB, (size_t)((width + 3) / 4) * height), s, args);
+            // 4 pixels of a row per thread, each row rounded up
+            void* args[] = {&lc.K, &G, &out, &ostride};
+            lc.run(K_BAKE_RGB, (size_t)((width + 3) / 4) * height, args);
         } else {
             LambdaSet L = make_lambda_set(lam_host, m);
-            void* args[] = {&K, &G, &L, &out, &ostride};
-            launch(e->fn(K_BAKE_SPEC, s), grid_for(e->mod, K_BAKE_SPEC, n), s, args);
+            void* args[] = {&lc.K, &G, &L, &out, &ostride};
+            lc.run(K_BAKE_SPEC, n, args);
         }
         hip_check(hipEventRecord(e->bake_done, s), "hipEventRecord");
     });
@@ -1337,14 +1273,11 @@ int sunsky_direct_diffuse(const sunsky_emitter* e, sunsky_vec3_in nrm, const flo
     if (ostride < n || (spec && lstride < n)) return fail(SUNSKY_ERROR_INVALID_VALUE, "stride < n");
     if (vis && vstride < n) return fail(SUNSKY_ERROR_INVALID_VALUE, "vis_stride < n");
     return guarded([&] {
-        require_device(e);
-        DeviceScope dev_scope(e->device);
-        const SunskyKArgs* K = e->d_state;
+        Launcher lc(e, stream);
         int nl = spec ? nlam : 0;
-        void* args[] = {&K, (void*)&nrm.x, (void*)&nrm.y, (void*)&nrm.z, &rho, &lam, &lstride, &nl, &seed, &spp, &vis,
+        void* args[] = {&lc.K, (void*)&nrm.x, (void*)&nrm.y, (void*)&nrm.z, &rho, &lam, &lstride, &nl, &seed, &spp, &vis,
                         &vstride, &n, &out, &ostride};
-        const KernelId k = spec ? K_DIRECT_DIFFUSE_SPEC : K_DIRECT_DIFFUSE_RGB;
-        launch(e->fn(k, (hipStream_t)stream), grid_for(e->mod, k, n), (hipStream_t)stream, args);
+        lc.run(spec ? K_DIRECT_DIFFUSE_SPEC : K_DIRECT_DIFFUSE_RGB, n, args);
     });
 }
 
@@ -1359,25 +1292,14 @@ int sunsky_direct_diffuse_rays(const sunsky_emitter* e, sunsky_vec3_in nrm, uint
     if (n > 0xffffffffull) return fail(SUNSKY_ERROR_INVALID_VALUE, "more than 2^32 points (the sampler's lane index is 32-bit)");
     if (rstride < n) return fail(SUNSKY_ERROR_INVALID_VALUE, "ray_stride < n");
     return guarded([&] {
-        require_device(e);
-        DeviceScope dev_scope(e->device);
-        const SunskyKArgs* K = e->d_state;
-        void* args[] = {&K, (void*)&nrm.x, (void*)&nrm.y, (void*)&nrm.z, &seed, &spp, &n, &em.x, &em.y, &em.z,
+        Launcher lc(e, stream);
+        void* args[] = {&lc.K, (void*)&nrm.x, (void*)&nrm.y, (void*)&nrm.z, &seed, &spp, &n, &em.x, &em.y, &em.z,
                         &bs.x, &bs.y, &bs.z, &rstride};
-        launch(e->fn(K_DIRECT_DIFFUSE_RAYS, (hipStream_t)stream), grid_for(e->mod, K_DIRECT_DIFFUSE_RAYS, n), (hipStream_t)stream, args);
+        lc.run(K_DIRECT_DIFFUSE_RAYS, n, args);
     });
 }
 
-// The rough conductor of the glossy caller (mirrors the kernel-side ConductorArgs; alpha_v
-// after the IOR so the isotropic layout's offsets stay)
-struct ConductorArgs {
-    int type;
-    float alpha_u;
-    float eta[4], k[4];
-    float alpha_v;
-};
-static_assert(sizeof(ConductorArgs) == 44 && offsetof(ConductorArgs, alpha_v) == 40, "ConductorArgs layout");
-
+// The rough conductor of the glossy caller (ConductorArgs, sunsky_kernel_args.h)
 static int conductor_args(const sunsky_emitter* e, int distribution, float alpha_u, float alpha_v, const float* eta,
                           const float* k, ConductorArgs* c) {
     if (distribution != SUNSKY_MICROFACET_BECKMANN && distribution != SUNSKY_MICROFACET_GGX)
@@ -1416,14 +1338,11 @@ static int direct_conductor_impl(const sunsky_emitter* e, sunsky_vec3_in nrm, su
     if (ostride < n || (spec && lstride < n)) return fail(SUNSKY_ERROR_INVALID_VALUE, "stride < n");
     if (vis && vstride < n) return fail(SUNSKY_ERROR_INVALID_VALUE, "vis_stride < n");
     return guarded([&] {
-        require_device(e);
-        DeviceScope dev_scope(e->device);
-        const SunskyKArgs* K = e->d_state;
+        Launcher lc(e, stream);
         int nl = spec ? nlam : 0;
-        void* args[] = {&K, &C, (void*)&nrm.x, (void*)&nrm.y, (void*)&nrm.z, (void*)&wi.x, (void*)&wi.y, (void*)&wi.z,
+        void* args[] = {&lc.K, &C, (void*)&nrm.x, (void*)&nrm.y, (void*)&nrm.z, (void*)&wi.x, (void*)&wi.y, (void*)&wi.z,
                         &lam, &lstride, &nl, &seed, &spp, &vis, &vstride, &n, &out, &ostride};
-        const KernelId kid = spec ? K_DIRECT_CONDUCTOR_SPEC : K_DIRECT_CONDUCTOR_RGB;
-        launch(e->fn(kid, (hipStream_t)stream), grid_for(e->mod, kid, n), (hipStream_t)stream, args);
+        lc.run(spec ? K_DIRECT_CONDUCTOR_SPEC : K_DIRECT_CONDUCTOR_RGB, n, args);
     });
 }
 
@@ -1448,12 +1367,10 @@ static int direct_conductor_rays_impl(const sunsky_emitter* e, sunsky_vec3_in nr
     if (n > 0xffffffffull) return fail(SUNSKY_ERROR_INVALID_VALUE, "more than 2^32 points (the sampler's lane index is 32-bit)");
     if (rstride < n) return fail(SUNSKY_ERROR_INVALID_VALUE, "ray_stride < n");
     return guarded([&] {
-        require_device(e);
-        DeviceScope dev_scope(e->device);
-        const SunskyKArgs* K = e->d_state;
-        void* args[] = {&K, &C, (void*)&nrm.x, (void*)&nrm.y, (void*)&nrm.z, (void*)&wi.x, (void*)&wi.y, (void*)&wi.z,
+        Launcher lc(e, stream);
+        void* args[] = {&lc.K, &C, (void*)&nrm.x, (void*)&nrm.y, (void*)&nrm.z, (void*)&wi.x, (void*)&wi.y, (void*)&wi.z,
                         &seed, &spp, &n, &em.x, &em.y, &em.z, &bs.x, &bs.y, &bs.z, &rstride, &bw, &nw};
-        launch(e->fn(K_DIRECT_CONDUCTOR_RAYS, (hipStream_t)stream), grid_for(e->mod, K_DIRECT_CONDUCTOR_RAYS, n), (hipStream_t)stream, args);
+        lc.run(K_DIRECT_CONDUCTOR_RAYS, n, args);
     });
 }
 

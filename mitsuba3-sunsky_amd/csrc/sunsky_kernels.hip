@@ -24,6 +24,7 @@
 //    order with full-precision libm.  Both are parity-tested against the oracle.
 #include <hip/hip_runtime.h>
 
+#include "sunsky_kernel_args.h"
 #include "sunsky_math.h"
 #include "sunsky_staging.h"
 #include "sunsky_types.h"
@@ -944,12 +945,6 @@ __device__ __forceinline__ void stage_spec_dist(const SunskyKArgs& K, SpecDistLd
 // to channels (lo[k], lo[k] + 1, f[k]) computed on the host (wave-uniform).
 // out plane k at out + k * ostride.
 // ======================================================================
-struct LambdaSet {
-    int m;
-    int lo[kMaxBroadcastLambda];
-    float f[kMaxBroadcastLambda];   // < 0: invalid wavelength (output 0)
-};
-
 // The broadcast / node kernels' FAST disc lanes: in line in their channel loops the fp64 term
 // (four copies, one per direction of a lane) held them to 5-6 waves/SIMD (86 / 80 VGPRs), so a
 // lane that met a disc direction walks its steps again after the main loop instead: each
@@ -2691,13 +2686,6 @@ __device__ __forceinline__ void direct_diffuse_body(
 // Mitsuba's default sampling.  All in the point's shading frame Frame3f(n) (coordinate_system),
 // fp32 with the libm functions.
 // ======================================================================
-struct ConductorArgs {
-    int type;            // 0 Beckmann, 1 GGX (MicrofacetType)
-    float alpha_u;       // roughness along the frame's s (microfacet.h m_alpha_u)
-    float eta[4], k[4];  // complex IOR per RGB channel (spectral: eta[0], k[0] for every wavelength)
-    float alpha_v;       // roughness along t (= alpha_u: isotropic)
-};
-
 // MicrofacetDistribution::eval (microfacet.h:186-207).  FAST: products with 1 / alpha_u,
 // 1 / alpha_v and v_rcp_f32 / v_exp_f32 in place of the divisions and expf.
 template <bool FAST>
@@ -3106,8 +3094,6 @@ __device__ __forceinline__ void direct_diffuse_rays_body(
         }
     }
 }
-
-struct LatLong { int w, h; float theta0, dtheta, phi0, dphi; const float* tab; };
 
 __device__ __forceinline__ float3_ latlong_dir(const LatLong& G, size_t i) {
     const unsigned y = (unsigned)i / (unsigned)G.w, x = (unsigned)i - y * (unsigned)G.w;   // W * H < 2^31
@@ -4053,18 +4039,6 @@ SS_BAKE(sunsky_bake_latlong_rgb_ref, sunsky_bake_latlong_spec_ref, false)
 // caller's stream.  The host writes the rest of the state (geometry, TGMM) with an
 // async copy just before; launches that follow on the stream see the new state.
 // ======================================================================
-struct StageArgs {                 // mirrors the host-side struct (sunsky_capi.cpp)
-    SunskyKArgs* state;            // the emitter's device state (sky[], fsky[] written)
-    float* sun_table;              // its turbidity-lerped sun table (written)
-    const float* sky_params_ds;    // (10 T, 2 albedo, 6 ctrl, nch, 9)
-    const float* sky_rad_ds;       // (10, 2, 6, nch)
-    const float* sun_rad_ds;       // (10, sun_block)
-    RadianceStage rs;
-    float albedo[kNbWavelengths];
-    int nch, variant, sun_block;
-    float sky_scale;
-};
-
 // One workgroup: every sky coefficient / radiance entry, every sun-table entry, then
 // one thread per channel folds it (sunsky_staging.h: the host model's arithmetic).
 extern "C" __global__ __launch_bounds__(256) void sunsky_stage_radiance(StageArgs A) {
@@ -4086,8 +4060,6 @@ extern "C" __global__ __launch_bounds__(256) void sunsky_stage_radiance(StageArg
     }
 }
 
-constexpr int kQuadBlock = 256;    // one quadrature row per workgroup, one point per thread
-
 // Tangent tables of eval_jvp / eval_vjp (sunsky_staging.h TangentArgs): one float per
 // thread, fp64 Bezier derivatives of the device-resident datasets, the same code as the
 // host model's eval_tangent.
@@ -4095,17 +4067,6 @@ extern "C" __global__ __launch_bounds__(256) void sunsky_stage_tangent(TangentAr
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < A.total; idx += gridDim.x * blockDim.x)
         A.out[idx] = tangent_buffer_value(A, idx);
 }
-
-struct QuadArgs {                  // mirrors the host-side struct (sunsky_capi.cpp)
-    SunskyKArgs* state;
-    const float* qx;               // 200 Gauss-Legendre nodes / weights (fp32)
-    const float* qw;
-    float* rows;                   // [2][nq][nch] row sums (sky, sun)
-    int nq, nch;
-    float cie_y[kNbWavelengths];
-    float sky_scale, sun_scale;
-    int* status;                   // set to 1 by a rejected staging (negative wavelength-distribution entry)
-};
 
 // Workgroup j = quadrature row j, thread i = point (i, j): its direction terms once,
 // every channel's sky and sun terms, then a fixed-shape tree reduction over the row's

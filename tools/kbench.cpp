@@ -24,6 +24,7 @@
 #include <string>
 #include <vector>
 
+#include "sunsky_kernel_args.h"
 #include "sunsky_model.h"
 
 using namespace sunsky;
@@ -36,12 +37,6 @@ using namespace sunsky;
             std::exit(1);                                                                  \
         }                                                                                  \
     } while (0)
-
-struct LambdaSet {
-    int m;
-    int lo[kMaxBroadcastLambda];
-    float f[kMaxBroadcastLambda];
-};
 
 int main(int argc, char** argv) {
     if (argc < 7) {
@@ -99,7 +94,6 @@ int main(int argc, char** argv) {
     }
     const int nout = spec ? 11 : (rays || sspec) ? 4 : (mode == "pdf" ? 1 : 3);
     // conductor mode: normals (mostly facing up) and views in their upper hemisphere
-    struct ConductorArgs { int type; float alpha_u; float eta[4], k[4]; float alpha_v; };
     ConductorArgs cargs = {std::getenv("KB_BECKMANN") ? 0 : 1, 0.2f, {0.143f, 0.374f, 1.442f, 0.f}, {3.983f, 2.385f, 1.603f, 0.f},
                            0.2f};
     float *cnx = nullptr, *cny = nullptr, *cnz = nullptr, *cvx = nullptr, *cvy = nullptr, *cvz = nullptr;
