@@ -1055,7 +1055,8 @@ int sunsky_eval_jvp(const sunsky_emitter* e, int param, const float* tangent, in
     if (!e) return fail(SUNSKY_ERROR_INVALID_VALUE, "null emitter");
     if (!tangent) return fail(SUNSKY_ERROR_INVALID_VALUE, "null tangent");
     const bool spec = e->kargs.variant == kSpectral;
-    if (spec && (!lam || nlam < 1 || nlam > kMaxLambdaPerRay))
+    // an empty batch has no planes to point to (as sunsky_eval): only the count is checked then
+    if (spec && ((n && !lam) || nlam < 1 || nlam > kMaxLambdaPerRay))
         return fail(SUNSKY_ERROR_INVALID_VALUE, "spectral eval needs 1..16 wavelength planes");
     const size_t nout = spec ? (size_t)nlam : 3;
     if (n && (!wi.x || !wi.y || !wi.z || !out || !d_out))

@@ -62,7 +62,8 @@ def _v3(t):
 def run(variant, precision, inp):
     """Every batch entry point whose grid the kernel table sizes -> {name: numpy array}.
     eval, eval_direction, pdf_direction and eval_spectral_broadcast go through the C ABI with
-    pitched planes, so that one call is a 4-per-lane body of n - 3 and a scalar tail of 3."""
+    pitched planes, so that one call is a 4-per-lane body of n - 3 and a scalar tail of 3;
+    eval_jvp (one lane per direction) along a turbidity and a sun_direction tangent."""
     spec = variant == "spectral"
     em = ss.SunskyEmitter(EMITTER, variant, precision=precision)
     lib, h, st = ss.lib(), em._h, em._stream()
@@ -97,6 +98,10 @@ def run(variant, precision, inp):
             ss._capi.check(lib.sunsky_eval_spectral_broadcast(h, _v3(wi), (ctypes.c_float * len(wl))(*wl), len(wl), None,
                                                               n, o.data_ptr(), pitch, st))
             out[name] = o[:, :n]
+    # forward-mode AD: its grid is eval's (grid_for); the precision does not select a kernel
+    si = ss.SurfaceInteraction3f(wi=-t["wo"], wavelengths=lam)
+    for name, param, tangent in (("jvp_turbidity", "turbidity", [1.0]), ("jvp_sun", "sun_direction", [0.3, -0.2, 0.5])):
+        out[name + "_val"], out[name + "_dval"] = em.eval_jvp(si, param, tangent)
     torch.cuda.synchronize()
     return {k: v.contiguous().cpu().numpy() for k, v in out.items()}
 

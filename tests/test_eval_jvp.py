@@ -49,6 +49,10 @@ def test_jvp_argument_validation_host():
     assert b"turbidity tangent" in lib.sunsky_last_error()
     assert lib.sunsky_eval_jvp(em._h, 1, t, 3, vin, None, 0, 0, None, 0, None, None, 0, None) == 0
     assert lib.sunsky_eval_jvp(em._h, 7, t, 1, vin, None, 0, 0, None, 0, None, None, 0, None) != 0
+    # an empty spectral batch has no wavelength planes to point to; the plane count is still checked
+    spec = ss.SunskyEmitter(scene(), "spectral", device="host")
+    assert lib.sunsky_eval_jvp(spec._h, 0, t, 1, vin, None, 4, 0, None, 0, None, None, 0, None) == 0
+    assert lib.sunsky_eval_jvp(spec._h, 0, t, 1, vin, None, 0, 0, None, 0, None, None, 0, None) != 0
     hour = ss.SunskyEmitter({"type": "sunsky", "hour": 12.0}, "rgb", device="host")
     assert lib.sunsky_eval_jvp(hour._h, 2, t, 3, vin, None, 0, 0, None, 0, None, None, 0, None) != 0
     assert b"time/location" in lib.sunsky_last_error()
