@@ -17,7 +17,8 @@
  *   - `stream` is a hipStream_t (NULL = default stream); every batch call is
  *     asynchronous and stream-ordered.  The hot-path calls (eval,
  *     eval_direction, eval_spectral_broadcast, sample_direction, pdf_direction,
- *     sample_ray, sample_wavelengths, direct_diffuse, direct_diffuse_rays)
+ *     sample_ray, sample_wavelengths, direct_diffuse, direct_diffuse_rays,
+ *     eval_jvp_dir, eval_vjp_dir)
  *     allocate nothing, make no host-synchronous call and may be captured into
  *     a hipGraph (tests/test_graph_capture.py).  Kernels read the emitter state
  *     from device memory, which parameters_changed_async rewrites in place on
@@ -47,7 +48,9 @@ extern "C" {
                                      5: direct_conductor(_rays)_aniso (alpha_u, alpha_v);
                                      6: SUNSKY_TABLE_SUN_SKY_FIT, emitter_inject_staging_fault (testing),
                                         a rejected update reverts to the last accepted one;
-                                     7: SUNSKY_TABLE_SUN_SEGMENTS, emitter_sun_segments (testing) */
+                                     7: SUNSKY_TABLE_SUN_SEGMENTS, emitter_sun_segments (testing);
+                                        added since, additive only (the version stays 7):
+                                        eval_jvp_dir, eval_vjp_dir */
 
 typedef enum sunsky_status {
     SUNSKY_OK = 0,
@@ -357,6 +360,27 @@ int sunsky_eval_jvp(const sunsky_emitter *e, int param, const float *tangent, in
 int sunsky_eval_vjp(const sunsky_emitter *e, sunsky_vec3_in wi, const float *wavelengths, int n_wavelengths,
                     size_t wl_stride, const uint8_t *active, size_t n, const float *d_out, size_t out_stride,
                     float *grad, void *stream);
+/* Derivatives of eval(si) with respect to its per-ray input si.wi -- what Dr.Jit traces
+ * through eval (sunsky.cpp:303-352) for a differentiable wi.  The function differentiated is
+ * eval as written: wo = to_world^-1(-wi) (linear part), cos theta = wo.z,
+ * gamma = unit_angle(sun, wo); nothing is renormalised, so the derivative has a radial
+ * component.  Masks (horizon, sun-disc test, elevation segment, wavelength validity) are not
+ * differentiated.  Inactive lanes (mask, cos theta < 0) and invalid wavelengths give exact
+ * zeros in every output.  Reference precision.  Layout and validation as sunsky_eval /
+ * sunsky_eval_jvp.  Both calls read only the emitter's device state: they are hot-path calls
+ * (stream-ordered, no allocation, no host-synchronous call, capturable).
+ *
+ * Forward: out = eval(si), d_out = (d eval / d wi) . d_wi, planes as out. */
+int sunsky_eval_jvp_dir(const sunsky_emitter *e, sunsky_vec3_in wi, sunsky_vec3_in d_wi,
+                        const float *wavelengths, int n_wavelengths, size_t wl_stride,
+                        const uint8_t *active, size_t n, float *out, float *d_out,
+                        size_t out_stride, void *stream);
+/* Reverse: grad_wi[ray] = sum over output planes of d_out * d eval / d wi (3 planes of n,
+ * overwritten, not accumulated; per ray, no reduction). */
+int sunsky_eval_vjp_dir(const sunsky_emitter *e, sunsky_vec3_in wi,
+                        const float *wavelengths, int n_wavelengths, size_t wl_stride,
+                        const uint8_t *active, size_t n, const float *d_out,
+                        size_t out_stride, sunsky_vec3_out grad_wi, void *stream);
 /* The tangent of the staged tables along `tangent` of `param` -- what dr::forward_from(param)
  * propagates into compute_radiance_params / compute_sun_params (sunsky.h:158-231, 404-419)
  * before eval: SUNSKY_TANGENT_FLOATS floats, d{A..I, rad} of channel c at c * 10 (+ q), the

@@ -199,6 +199,23 @@ public:
         check(sunsky_eval_vjp(e_, vin(si.wi), si.wavelengths.data, si.wavelengths.count, si.wavelengths.stride,
                               active, si.n, d_out, d_out_stride ? d_out_stride : si.n, grad, stream));
     }
+    // eval(si) and its forward-mode derivative with respect to the ray direction si.wi along the
+    // per-ray tangent d_wi (sunsky_eval_jvp_dir): eval as written, reference precision.  A
+    // hot-path call: stream-ordered, capturable.
+    void eval_jvp_dir(const SurfaceInteraction& si, const Vector3& d_wi, SpectrumOut out, SpectrumOut d_out,
+                      const uint8_t* active = nullptr, void* stream = nullptr) const {
+        const size_t stride = out.stride ? out.stride : si.n;
+        if ((d_out.stride ? d_out.stride : si.n) != stride)
+            throw Error(SUNSKY_ERROR_INVALID_VALUE, "out and d_out must share one plane stride");
+        check(sunsky_eval_jvp_dir(e_, vin(si.wi), vin(d_wi), si.wavelengths.data, si.wavelengths.count,
+                                  si.wavelengths.stride, active, si.n, out.data, d_out.data, stride, stream));
+    }
+    // Reverse mode: grad_wi[ray] = sum over planes of d_out * d eval(si) / d wi (overwritten)
+    void eval_vjp_dir(const SurfaceInteraction& si, const float* d_out, size_t d_out_stride, const Vector3Out& grad_wi,
+                      const uint8_t* active = nullptr, void* stream = nullptr) const {
+        check(sunsky_eval_vjp_dir(e_, vin(si.wi), si.wavelengths.data, si.wavelengths.count, si.wavelengths.stride,
+                                  active, si.n, d_out, d_out_stride ? d_out_stride : si.n, vout(grad_wi), stream));
+    }
     // Lat-long environment map of the sky (sunsky_bake_latlong): planes [c][height * width]
     void bake_latlong(int width, int height, float theta0, float theta1, float phi0, float phi1, SpectrumOut out,
                       const std::vector<float>& wavelengths = {}, void* stream = nullptr) const {

@@ -178,6 +178,8 @@ struct DeviceModule {
     hipFunction_t fn_dir[2][2][K_COUNT] = {};   // eval_direction forms (wo = +d) of the eval kernels
     hipFunction_t jvp_rgb = nullptr, jvp_spec = nullptr;   // eval_jvp (reference operation order)
     hipFunction_t vjp_rgb = nullptr, vjp_spec = nullptr, grad_reduce = nullptr;   // eval_vjp
+    hipFunction_t jvp_dir_rgb = nullptr, jvp_dir_spec = nullptr;   // eval_jvp_dir / eval_vjp_dir (d eval / d wi)
+    hipFunction_t vjp_dir_rgb = nullptr, vjp_dir_spec = nullptr;
     hipFunction_t latlong_tables = nullptr;                                     // bake_latlong
     hipFunction_t stage_radiance = nullptr, quad_points = nullptr, quad_finish = nullptr;   // parameters_changed
     hipFunction_t stage_tangent = nullptr;                                      // eval_jvp / eval_vjp tables
@@ -215,6 +217,10 @@ DeviceModule* module_for_device(int dev) {
     get(&m->vjp_rgb, m->module, "sunsky_eval_vjp_rgb");
     get(&m->vjp_spec, m->module, "sunsky_eval_vjp_spec");
     get(&m->grad_reduce, m->module, "sunsky_grad_reduce");
+    get(&m->jvp_dir_rgb, m->module, "sunsky_eval_jvp_dir_rgb");
+    get(&m->jvp_dir_spec, m->module, "sunsky_eval_jvp_dir_spec");
+    get(&m->vjp_dir_rgb, m->module, "sunsky_eval_vjp_dir_rgb");
+    get(&m->vjp_dir_spec, m->module, "sunsky_eval_vjp_dir_spec");
     get(&m->latlong_tables, m->module, "sunsky_latlong_tables");
     get(&m->stage_tangent, m->module, "sunsky_stage_tangent");
     get(&m->stage_radiance, m->module, "sunsky_stage_radiance");
@@ -1202,6 +1208,67 @@ int sunsky_eval_vjp(const sunsky_emitter* e, sunsky_vec3_in wi, const float* lam
         void* rargs[] = {&partials, &nb, &grad};
         launch(e->mod->grad_reduce, 1, st, rargs);
         e->ad_end(st);
+    });
+}
+
+// d eval / d wi: argument checks shared by the two calls (sunsky_eval_jvp's rules)
+static int dir_ad_check(const sunsky_emitter* e, sunsky_vec3_in wi, const float* lam, int nlam, size_t lstride,
+                        size_t n, bool planes_ok, size_t ostride) {
+    if (!e) return fail(SUNSKY_ERROR_INVALID_VALUE, "null emitter");
+    const bool spec = e->kargs.variant == kSpectral;
+    // an empty batch has no planes to point to (as sunsky_eval_jvp): only the count is checked then
+    if (spec && ((n && !lam) || nlam < 1 || nlam > kMaxLambdaPerRay))
+        return fail(SUNSKY_ERROR_INVALID_VALUE, "spectral eval needs 1..16 wavelength planes");
+    const size_t nout = spec ? (size_t)nlam : 3;
+    if (n && (!wi.x || !wi.y || !wi.z || !planes_ok))
+        return fail(SUNSKY_ERROR_INVALID_VALUE, "null ray / tangent / output pointer");
+    if (n && nout > 1 && ostride < n) return fail(SUNSKY_ERROR_INVALID_VALUE, "out_stride < n");
+    if (n && spec && nlam > 1 && lstride < n) return fail(SUNSKY_ERROR_INVALID_VALUE, "wl_stride < n");
+    return SUNSKY_OK;
+}
+
+int sunsky_eval_jvp_dir(const sunsky_emitter* e, sunsky_vec3_in wi, sunsky_vec3_in d_wi, const float* lam, int nlam,
+                        size_t lstride, const uint8_t* active, size_t n, float* out, float* d_out, size_t ostride,
+                        void* stream) {
+    SUNSKY_PHASE("EndpointEvaluate", "eval_jvp_dir");
+    if (int rc = dir_ad_check(e, wi, lam, nlam, lstride, n, d_wi.x && d_wi.y && d_wi.z && out && d_out, ostride))
+        return rc;
+    if (n == 0) return SUNSKY_OK;
+    return guarded([&] {
+        Launcher lc(e, stream);
+        const float *x = wi.x, *y = wi.y, *z = wi.z, *dx = d_wi.x, *dy = d_wi.y, *dz = d_wi.z;
+        float sign = -1.f;
+        if (e->kargs.variant != kSpectral) {
+            void* args[] = {&lc.K, &x, &y, &z, &dx, &dy, &dz, &active, &n, &out, &d_out, &ostride, &sign};
+            launch(e->mod->jvp_dir_rgb, grid_for(e->mod, K_EVAL_RGB_V1, n), lc.s, args);
+        } else {
+            int nl = nlam;
+            void* args[] = {&lc.K, &x, &y, &z, &dx, &dy, &dz, &lam, &lstride, &nl, &active, &n, &out, &d_out, &ostride, &sign};
+            launch(e->mod->jvp_dir_spec, grid_for(e->mod, K_EVAL_SPEC_RAYS_V1, n), lc.s, args);
+        }
+    });
+}
+
+int sunsky_eval_vjp_dir(const sunsky_emitter* e, sunsky_vec3_in wi, const float* lam, int nlam, size_t lstride,
+                        const uint8_t* active, size_t n, const float* d_out, size_t ostride, sunsky_vec3_out grad_wi,
+                        void* stream) {
+    SUNSKY_PHASE("EndpointEvaluate", "eval_vjp_dir");
+    if (int rc = dir_ad_check(e, wi, lam, nlam, lstride, n, d_out && grad_wi.x && grad_wi.y && grad_wi.z, ostride))
+        return rc;
+    if (n == 0) return SUNSKY_OK;
+    return guarded([&] {
+        Launcher lc(e, stream);
+        const float *x = wi.x, *y = wi.y, *z = wi.z;
+        float *gx = grad_wi.x, *gy = grad_wi.y, *gz = grad_wi.z;
+        float sign = -1.f;
+        if (e->kargs.variant != kSpectral) {
+            void* args[] = {&lc.K, &x, &y, &z, &active, &n, &d_out, &ostride, &gx, &gy, &gz, &sign};
+            launch(e->mod->vjp_dir_rgb, grid_for(e->mod, K_EVAL_RGB_V1, n), lc.s, args);
+        } else {
+            int nl = nlam;
+            void* args[] = {&lc.K, &x, &y, &z, &lam, &lstride, &nl, &active, &n, &d_out, &ostride, &gx, &gy, &gz, &sign};
+            launch(e->mod->vjp_dir_spec, grid_for(e->mod, K_EVAL_SPEC_RAYS_V1, n), lc.s, args);
+        }
     });
 }
 

@@ -3669,6 +3669,283 @@ __device__ __forceinline__ void eval_vjp_spec_body(const SunskyKArgs& K, const f
 }
 
 // ======================================================================
+// eval_jvp_dir / eval_vjp_dir: the derivative of eval(si) with respect to its per-ray
+// input si.wi (sunsky.cpp:303-352 as written: wo = to_local(-wi), cos theta = wo.z,
+// gamma = unit_angle(sun, wo), nothing renormalised; the masks are not differentiated).
+// Per channel L depends on the direction through cos theta and gamma only, so each
+// channel forms dL/d cos theta and dL/d gamma once:
+//   forward: d L = dL/dcos * d wo.z + dL/dgamma * (d gamma/d wo . d wo), d wo = to_local(-d wi)
+//   reverse: grad wo = (sum_c cot_c dL_c/dcos) e_z + (sum_c cot_c dL_c/dgamma) d gamma/d wo,
+//            grad wi = -to_local^T grad wo -- one pass over the channels, two accumulators.
+// Only the emitter's device state is read: no tangent tables, nothing staged.
+// Conventions: inactive lanes and invalid wavelengths give exact zeros; d sqrt(cos theta) = 0
+// at cos theta = 0; d elevation = 0 where 1 - cos^2 theta <= 0; h = 0 gives d gamma = 0 and
+// cos psi <= 0 gives d cos psi = 0 (unit_angle_tan_setup, cos_psi_jvp).
+// ======================================================================
+struct DirAd {
+    DirTerms t;
+    float sg;         // sin(gamma)
+    float3_ gg;       // d gamma / d wo (the chord form of unit_angle_tan_setup, tangent on b)
+    int pos;          // sun-disc lanes: elevation segment, x, cos psi, d cos psi / d gamma,
+    float xs, cp, dcp, de;   // d elevation / d cos theta
+};
+
+__device__ __forceinline__ DirAd dir_ad(const SunskyKArgs& K, float3_ wo, bool m) {
+    DirAd d;
+    d.t = dir_terms<false>(K, wo, m);
+    d.sg = sin_gamma(d.t);
+    const UnitAngleTan ua = unit_angle_tan_setup(mk3(K.sun_n[0], K.sun_n[1], K.sun_n[2]), wo);
+    d.gg = mk3(ua.v.x * ua.f, ua.v.y * ua.f, ua.v.z * ua.f);
+    d.pos = 0;
+    d.xs = d.cp = d.dcp = d.de = 0.f;
+    if (d.t.hit_sun) {
+        d.pos = sun_segment_ref(K, d.t.cos_theta, &d.xs);
+        cos_psi_jvp(K, d.t, d.sg, 1.f, &d.cp, &d.dcp);
+        const float s2 = 1.f - d.t.cos_theta * d.t.cos_theta;   // elevation = pi/2 - acos(cos theta)
+        d.de = s2 > 0.f ? 1.f / sqrtf(s2) : 0.f;
+    }
+    return d;
+}
+
+// One channel's value and its two partial derivatives
+struct ChanD { float v, dc, dg; };   // L, dL / d cos theta, dL / d gamma
+
+// render_sky (unscaled): the gamma part is sky_tan_gamma; cos theta enters through
+// r = 1 / (cos theta + 0.01) (d r = -r^2) in e1 = exp(B r), and through sqrt(cos theta)
+__device__ __forceinline__ ChanD sky_dir(const SkyChannel& k, const DirTerms& t, float sg) {
+    const SkyVal s = sky_val(k, t);
+    ChanD r;
+    r.v = s.c1 * s.c2 * k.rad;
+    r.dg = sky_tan_gamma(k, t, s, sg);
+    const float dc1 = -(k.A * s.e1 * k.B * t.r * t.r);
+    const float dc2 = t.cos_theta > 0.f ? k.H * (0.5f / t.sq) : 0.f;
+    r.dc = (dc1 * s.c2 + s.c1 * dc2) * k.rad;
+    return r;
+}
+
+// eval's RGB channel c (before the CIE normalisation), eval_jvp_rgb_body's operation order
+__device__ __forceinline__ ChanD chan_dir_rgb(const SunskyKArgs& K, const DirAd& d, int c) {
+    ChanD r = sky_dir(K.sky[c], d.t, d.sg);
+    r.v *= K.sky_scale;
+    r.dc *= K.sky_scale;
+    r.dg *= K.sky_scale;
+    if (d.t.hit_sun) {
+        const float* S = K.sun_table + d.pos * (3 * kNbSunCtrlPts * kNbSunLdParams) + c * (kNbSunCtrlPts * kNbSunLdParams);
+        float sv = 0.f, dX = 0.f, dC = 0.f;   // value, d / d x, d / d cos psi
+#pragma unroll 1
+        for (int k = 0; k < kNbSunCtrlPts; ++k) {
+            const float xk = powif_(d.xs, k), dxk = k > 0 ? (float)k * powif_(d.xs, k - 1) : 0.f;
+#pragma unroll 1
+            for (int j = 0; j < kNbSunLdParams; ++j) {
+                const float cj = powif_(d.cp, j), s = S[k * kNbSunLdParams + j];
+                sv += xk * cj * s;
+                dX += dxk * cj * s;
+                if (j > 0) dC += xk * (float)j * powif_(d.cp, j - 1) * s;
+            }
+        }
+        const float sc = K.sun_scale * K.area_ratio * (float)kSpecToRgbSunConv;
+        r.v += sc * sv;
+        r.dc += sc * dX * d.de;
+        r.dg += sc * dC * d.dcp;
+    }
+    return r;
+}
+
+// d render_sun_spec / d x
+__device__ __forceinline__ float render_sun_spec_dx(const float* table, int pos, int c, float x) {
+    const float* s = table + pos * (kNbWavelengths * kNbSunCtrlPts) + c * kNbSunCtrlPts;
+    float res = 0.f;
+#pragma unroll 1
+    for (int k = 1; k < kNbSunCtrlPts; ++k) res += (float)k * powif_(x, k - 1) * s[k];
+    return res;
+}
+
+// eval at one wavelength of a lane (nw: its normalised wavelength, valid), eval_jvp_spec_body's
+// operation order; the channel constants from LDS
+__device__ __forceinline__ ChanD chan_dir_spec(const SunskyKArgs& K, const SkyChannel* sky, const DirAd& d, float nw) {
+    const int lo = (int)floorf(nw), hi = lo + 1;
+    const float f = nw - (float)lo;
+    const ChanD a = sky_dir(sky[lo], d.t, d.sg);
+    ChanD b = {0.f, 0.f, 0.f};
+    if (hi < kNbWavelengths) b = sky_dir(sky[hi], d.t, d.sg);
+    ChanD r;
+    r.v = K.sky_scale * (f != 0.f ? lerpf_(a.v, b.v, f) : a.v);
+    r.dc = K.sky_scale * (f != 0.f ? lerpf_(a.dc, b.dc, f) : a.dc);
+    r.dg = K.sky_scale * (f != 0.f ? lerpf_(a.dg, b.dg, f) : a.dg);
+    if (d.t.hit_sun) {
+        float sun = render_sun_spec(K.sun_table, d.pos, lo, d.xs), dsun = render_sun_spec_dx(K.sun_table, d.pos, lo, d.xs);
+        if (f != 0.f) {
+            const float sb = hi < kNbWavelengths ? render_sun_spec(K.sun_table, d.pos, hi, d.xs) : 0.f;
+            const float dsb = hi < kNbWavelengths ? render_sun_spec_dx(K.sun_table, d.pos, hi, d.xs) : 0.f;
+            sun = lerpf_(sun, sb, f);
+            dsun = lerpf_(dsun, dsb, f);
+        }
+        const float ld = sun_limb_darkening(K.sun_ld, lo, hi, f, d.cp);
+        float dld = 0.f;   // d limb darkening / d cos psi
+#pragma unroll 1
+        for (int j = 1; j < kNbSunLdParams; ++j) {
+            const float c0 = K.sun_ld[lo * kNbSunLdParams + j];
+            float coef = c0;
+            if (f != 0.f) coef = lerpf_(c0, hi < kNbWavelengths ? K.sun_ld[hi * kNbSunLdParams + j] : 0.f, f);
+            dld += (float)j * powif_(d.cp, j - 1) * coef;
+        }
+        const float sc = K.sun_scale * K.area_ratio;
+        r.v += K.sun_scale * sun * ld * K.area_ratio;
+        r.dc += sc * (dsun * d.de * ld);
+        r.dg += sc * (sun * dld * d.dcp);
+    }
+    return r;
+}
+
+// grad wi = sign * to_local^T grad wo (wo = to_local(sign * wi))
+__device__ __forceinline__ float3_ to_local_transposed(const SunskyKArgs& K, float3_ g) {
+#ifdef SS_XFORM_IDENTITY
+    (void)K;
+    return g;
+#else
+    if (K.identity_xform) return g;
+    const float* m = K.to_local;
+    return mk3(fmaf(m[6], g.z, fmaf(m[3], g.y, m[0] * g.x)),
+               fmaf(m[7], g.z, fmaf(m[4], g.y, m[1] * g.x)),
+               fmaf(m[8], g.z, fmaf(m[5], g.y, m[2] * g.x)));
+#endif
+}
+
+struct DirAdLds { SkyChannel sky[kNbWavelengths]; };   // per-lane channel index (see JvpLds)
+
+__device__ __forceinline__ bool wavelength_valid(float lambda, float* nw) {
+    *nw = (lambda - kWavelength0) / kWavelengthStep;
+    return (0.f <= *nw) && (*nw <= (float)(kNbWavelengths - 1));   // false for NaN
+}
+
+__device__ __forceinline__ void eval_jvp_dir_rgb_body(const SunskyKArgs& K, const float* __restrict__ wx,
+                                                      const float* __restrict__ wy, const float* __restrict__ wz,
+                                                      const float* __restrict__ dx, const float* __restrict__ dy,
+                                                      const float* __restrict__ dz, const uint8_t* __restrict__ active,
+                                                      size_t n, float* __restrict__ out, float* __restrict__ dout,
+                                                      size_t ostride, float sign) {
+    const float cie = (float)kCieYNormalization;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const bool m = active ? active[i] != 0 : true;
+        const float3_ wo = to_local(K, mk3(sign * wx[i], sign * wy[i], sign * wz[i]));
+        const float3_ dwo = to_local(K, mk3(sign * dx[i], sign * dy[i], sign * dz[i]));
+        const DirAd d = dir_ad(K, wo, m);
+        const float dct = dwo.z, dgm = dot3(d.gg, dwo);
+        float v[3], dv[3];
+#pragma unroll 1
+        for (int c = 0; c < 3; ++c) {
+            const ChanD r = chan_dir_rgb(K, d, c);
+            v[c] = r.v;
+            dv[c] = r.dc * dct + r.dg * dgm;
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            out[(size_t)c * ostride + i] = d.t.active ? v[c] * cie : 0.f;
+            dout[(size_t)c * ostride + i] = d.t.active ? dv[c] * cie : 0.f;
+        }
+    }
+}
+
+__device__ __forceinline__ void eval_vjp_dir_rgb_body(const SunskyKArgs& K, const float* __restrict__ wx,
+                                                      const float* __restrict__ wy, const float* __restrict__ wz,
+                                                      const uint8_t* __restrict__ active, size_t n,
+                                                      const float* __restrict__ dout, size_t ostride,
+                                                      float* __restrict__ gx, float* __restrict__ gy,
+                                                      float* __restrict__ gz, float sign) {
+    const float cie = (float)kCieYNormalization;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const bool m = active ? active[i] != 0 : true;
+        const float3_ wo = to_local(K, mk3(sign * wx[i], sign * wy[i], sign * wz[i]));
+        const DirAd d = dir_ad(K, wo, m);
+        float3_ g = mk3(0.f, 0.f, 0.f);
+        if (d.t.active) {
+            float a = 0.f, b = 0.f;   // sum_c cot_c dL_c / d cos theta, sum_c cot_c dL_c / d gamma
+#pragma unroll 1
+            for (int c = 0; c < 3; ++c) {
+                const float cot = dout[(size_t)c * ostride + i] * cie;
+                const ChanD r = chan_dir_rgb(K, d, c);
+                a += cot * r.dc;
+                b += cot * r.dg;
+            }
+            const float3_ gw = to_local_transposed(K, mk3(b * d.gg.x, b * d.gg.y, fmaf(b, d.gg.z, a)));
+            g = mk3(sign * gw.x, sign * gw.y, sign * gw.z);
+        }
+        gx[i] = g.x;
+        gy[i] = g.y;
+        gz[i] = g.z;
+    }
+}
+
+__device__ __forceinline__ void eval_jvp_dir_spec_body(const SunskyKArgs& K, const float* __restrict__ wx,
+                                                       const float* __restrict__ wy, const float* __restrict__ wz,
+                                                       const float* __restrict__ dx, const float* __restrict__ dy,
+                                                       const float* __restrict__ dz, const float* __restrict__ lam,
+                                                       size_t lstride, int nlam, const uint8_t* __restrict__ active,
+                                                       size_t n, float* __restrict__ out, float* __restrict__ dout,
+                                                       size_t ostride, float sign) {
+    __shared__ DirAdLds S;
+    lds_copy(S.sky, K.sky, kNbWavelengths);
+    __syncthreads();
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const bool m = active ? active[i] != 0 : true;
+        const float3_ wo = to_local(K, mk3(sign * wx[i], sign * wy[i], sign * wz[i]));
+        const float3_ dwo = to_local(K, mk3(sign * dx[i], sign * dy[i], sign * dz[i]));
+        const DirAd d = dir_ad(K, wo, m);
+        const float dct = dwo.z, dgm = dot3(d.gg, dwo);
+#pragma unroll 1
+        for (int q = 0; q < nlam; ++q) {
+            float nw, res = 0.f, dres = 0.f;
+            if (wavelength_valid(lam[(size_t)q * lstride + i], &nw) && d.t.active) {
+                const ChanD r = chan_dir_spec(K, S.sky, d, nw);
+                res = r.v;
+                dres = r.dc * dct + r.dg * dgm;
+            }
+            out[(size_t)q * ostride + i] = res;
+            dout[(size_t)q * ostride + i] = dres;
+        }
+    }
+}
+
+__device__ __forceinline__ void eval_vjp_dir_spec_body(const SunskyKArgs& K, const float* __restrict__ wx,
+                                                       const float* __restrict__ wy, const float* __restrict__ wz,
+                                                       const float* __restrict__ lam, size_t lstride, int nlam,
+                                                       const uint8_t* __restrict__ active, size_t n,
+                                                       const float* __restrict__ dout, size_t ostride,
+                                                       float* __restrict__ gx, float* __restrict__ gy,
+                                                       float* __restrict__ gz, float sign) {
+    __shared__ DirAdLds S;
+    lds_copy(S.sky, K.sky, kNbWavelengths);
+    __syncthreads();
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const bool m = active ? active[i] != 0 : true;
+        const float3_ wo = to_local(K, mk3(sign * wx[i], sign * wy[i], sign * wz[i]));
+        const DirAd d = dir_ad(K, wo, m);
+        float3_ g = mk3(0.f, 0.f, 0.f);
+        if (d.t.active) {
+            float a = 0.f, b = 0.f;
+#pragma unroll 1
+            for (int q = 0; q < nlam; ++q) {
+                float nw;
+                if (!wavelength_valid(lam[(size_t)q * lstride + i], &nw)) continue;
+                const float cot = dout[(size_t)q * ostride + i];
+                const ChanD r = chan_dir_spec(K, S.sky, d, nw);
+                a += cot * r.dc;
+                b += cot * r.dg;
+            }
+            const float3_ gw = to_local_transposed(K, mk3(b * d.gg.x, b * d.gg.y, fmaf(b, d.gg.z, a)));
+            g = mk3(sign * gw.x, sign * gw.y, sign * gw.z);
+        }
+        gx[i] = g.x;
+        gy[i] = g.y;
+        gz[i] = g.z;
+    }
+}
+
+// ======================================================================
 // extern "C" entry points (hipModuleGetFunction names)
 // ======================================================================
 #define SS_EVAL_RGB(NAME, VEC, FAST, NEG)                                                                          \
@@ -4019,7 +4296,31 @@ extern "C" __global__ __launch_bounds__(256) void sunsky_grad_reduce(const float
     }
 }
 
-#define SS_BAKE(NAME_RGB, NAME_SPEC, FAST)                                                                    \
+// eval_jvp_dir / eval_vjp_dir (d eval / d wi): per ray, reference precision
+extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_eval_jvp_dir_rgb(
+    const SunskyKArgs* __restrict__ Kp, const float* wx, const float* wy, const float* wz, const float* dx, const float* dy,
+    const float* dz, const uint8_t* active, size_t n, float* out, float* dout, size_t ostride, float sign) {
+    eval_jvp_dir_rgb_body(*Kp, wx, wy, wz, dx, dy, dz, active, n, out, dout, ostride, sign);
+}
+extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_eval_jvp_dir_spec(
+    const SunskyKArgs* __restrict__ Kp, const float* wx, const float* wy, const float* wz, const float* dx, const float* dy,
+    const float* dz, const float* lam, size_t lstride, int nlam, const uint8_t* active, size_t n, float* out, float* dout,
+    size_t ostride, float sign) {
+    eval_jvp_dir_spec_body(*Kp, wx, wy, wz, dx, dy, dz, lam, lstride, nlam, active, n, out, dout, ostride, sign);
+}
+extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_eval_vjp_dir_rgb(
+    const SunskyKArgs* __restrict__ Kp, const float* wx, const float* wy, const float* wz, const uint8_t* active, size_t n,
+    const float* dout, size_t ostride, float* gx, float* gy, float* gz, float sign) {
+    eval_vjp_dir_rgb_body(*Kp, wx, wy, wz, active, n, dout, ostride, gx, gy, gz, sign);
+}
+extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_eval_vjp_dir_spec(
+    const SunskyKArgs* __restrict__ Kp, const float* wx, const float* wy, const float* wz, const float* lam, size_t lstride,
+    int nlam, const uint8_t* active, size_t n, const float* dout, size_t ostride, float* gx, float* gy, float* gz,
+    float sign) {
+    eval_vjp_dir_spec_body(*Kp, wx, wy, wz, lam, lstride, nlam, active, n, dout, ostride, gx, gy, gz, sign);
+}
+
+#define SS_BAKE(NAME_RGB, NAME_SPEC, FAST)                                                                   \
     extern "C" __global__ __launch_bounds__(SS_BLOCK) void NAME_RGB(const SunskyKArgs* __restrict__ Kp, LatLong G, float* out,      \
                                                                     size_t ostride) {                          \
         bake_rgb_body<FAST>(*Kp, G, out, ostride);                                                               \

@@ -439,6 +439,50 @@ class SunskyEmitter:
                 "sun_direction": grad[_capi.GRAD_SUN_DIRECTION:_capi.GRAD_SUN_DIRECTION + 3]}
         return grad, view
 
+    def _dir_ad_inputs(self, si, active):
+        wi, vin = self._vec_in(si.wi, name="si.wi")
+        n = wi.shape[1]
+        m = self._mask(active, n)
+        wl, k = None, 3
+        if self.is_spectral:
+            wl = self._wavelengths(getattr(si, "wavelengths", None), n)
+            k = wl.shape[0]
+        return wi, vin, n, m, wl, k
+
+    @staticmethod
+    def _require_f32(t, name):
+        if isinstance(t, torch.Tensor) and t.dtype != torch.float32:
+            raise ValueError(f"{name} must be float32, got {t.dtype}")
+
+    def eval_jvp_dir(self, si, d_wi, active=None):
+        """Forward-mode derivative of eval(si) with respect to the ray direction si.wi along
+        the per-ray tangent `d_wi` (3, n): eval as written (wo = to_world^-1(-wi), not
+        renormalised; masks are not differentiated), reference precision.  A hot-path call:
+        stream-ordered, graph-capturable.  -> (value, d_value), each (3, n) or (k, n)."""
+        self._require_f32(d_wi, "d_wi")
+        wi, vin, n, m, wl, k = self._dir_ad_inputs(si, active)
+        d_wi, din = self._vec_in(d_wi, n, name="d_wi")
+        out = torch.empty((k, n), dtype=torch.float32, device=self.device)
+        dout = torch.empty((k, n), dtype=torch.float32, device=self.device)
+        check(lib().sunsky_eval_jvp_dir(self._h, vin, din, _ptr(wl), k if self.is_spectral else 0, n, _ptr(m), n,
+                                        _ptr(out), _ptr(dout), n, self._stream()))
+        return out, dout
+
+    def eval_vjp_dir(self, si, d_out, active=None, out=None):
+        """Reverse mode of eval(si) with respect to si.wi: grad_wi (3, n), per ray
+        sum_c d_out[c] * d eval_c / d wi (written to `out` if given, overwriting it).  Inactive
+        lanes get exact zeros.  A hot-path call: stream-ordered, graph-capturable."""
+        self._require_f32(d_out, "d_out")
+        wi, vin, n, m, wl, k = self._dir_ad_inputs(si, active)
+        d_out = self._f32(d_out)
+        if tuple(d_out.shape) != (k, n):
+            raise ValueError(f"d_out must have shape ({k}, {n}), got {tuple(d_out.shape)}")
+        g = self._out(out, (3, n))
+        check(lib().sunsky_eval_vjp_dir(self._h, vin, _ptr(wl), k if self.is_spectral else 0, n, _ptr(m), n,
+                                        _ptr(d_out), n, Vec3Out(g[0].data_ptr(), g[1].data_ptr(), g[2].data_ptr()),
+                                        self._stream()))
+        return g
+
     def bake_latlong(self, width, height, theta=(0.0, math.pi), phi=(0.0, 2 * math.pi), wavelengths=None,
                      out=None):
         """Lat-long environment map of the emitter (sunsky_bake_latlong): (C, height, width),

@@ -1,5 +1,6 @@
-"""AD kernel timing helper (run under rocprofv3 --kernel-trace --stats): eval_vjp and
-eval_jvp over 16M upper-hemisphere directions, RGB and spectral (4 lambda per ray)."""
+"""AD kernel timing helper (run under rocprofv3 --kernel-trace --stats): eval_vjp, eval_jvp,
+eval_jvp_dir and eval_vjp_dir over 16M upper-hemisphere directions, RGB and spectral (4 lambda
+per ray).  AD_BENCH_DIR=0 leaves the two direction calls out (a build without them)."""
 import os
 import sys
 
@@ -25,5 +26,11 @@ for variant, k in (("rgb", 3), ("spectral", 4)):
         em.eval_vjp(si, cot, grad=grad)
     for _ in range(10):
         em.eval_jvp(si, "turbidity", [1.0])
+    if os.environ.get("AD_BENCH_DIR", "1") != "0":
+        d_wi = torch.randn((3, n), device=dev, generator=g)
+        grad_wi = torch.empty((3, n), device=dev)
+        for _ in range(11):   # the first launch of each warms up
+            em.eval_jvp_dir(si, d_wi)
+            em.eval_vjp_dir(si, cot, out=grad_wi)
     torch.cuda.synchronize()
 print("ad_bench done")
