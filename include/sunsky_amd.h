@@ -18,7 +18,7 @@
  *     asynchronous and stream-ordered.  The hot-path calls (eval,
  *     eval_direction, eval_spectral_broadcast, sample_direction, pdf_direction,
  *     sample_ray, sample_wavelengths, direct_diffuse, direct_diffuse_rays,
- *     eval_jvp_dir, eval_vjp_dir)
+ *     eval_jvp_dir, eval_vjp_dir, sequence_eval)
  *     allocate nothing, make no host-synchronous call and may be captured into
  *     a hipGraph (tests/test_graph_capture.py).  Kernels read the emitter state
  *     from device memory, which parameters_changed_async rewrites in place on
@@ -50,7 +50,8 @@ extern "C" {
                                         a rejected update reverts to the last accepted one;
                                      7: SUNSKY_TABLE_SUN_SEGMENTS, emitter_sun_segments (testing);
                                         added since, additive only (the version stays 7):
-                                        eval_jvp_dir, eval_vjp_dir */
+                                        eval_jvp_dir, eval_vjp_dir; sun_coordinates and the
+                                        sunsky_sequence_* calls (frame sequences) */
 
 typedef enum sunsky_status {
     SUNSKY_OK = 0,
@@ -253,6 +254,70 @@ int sunsky_sample_position(const sunsky_emitter *e);
 int sunsky_bake_latlong(const sunsky_emitter *e, int width, int height, float theta0, float theta1,
                         float phi0, float phi1, const float *wavelengths_host, int n_wavelengths,
                         float *out, size_t out_stride, void *stream);
+
+/* ------------------------------------------------------------ frame sequences
+ * A sequence is count >= 1 frames over a snapshot of one emitter: frame k has a world-space
+ * sun direction s_k, a turbidity T_k in [1, 10] and a weight w_k (finite, >= 0); variant,
+ * semantics, albedo, sky_scale, sun_scale, sun aperture, to_world and precision are the
+ * emitter's at creation.  One call returns, per ray and output plane,
+ *     out = sum_k w_k eval_k(wi)
+ * where eval_k is sunsky_eval of an emitter that equals the parent with sun_direction = s_k
+ * and turbidity = T_k: the same masks (horizon, per-frame sun-disc test), the same per-frame
+ * elevation segment, and in FAST precision the same fp64 disc term.  Frames are added in
+ * frame order in fp32 (fma(w_k, eval_k, acc)): the result is deterministic.  A frame whose sun
+ * is below the horizon behaves as that emitter does (sky coefficients 0; not an error).
+ * Inactive lanes (mask, or cos theta < 0) give exact zeros.  The sequence keeps no pointer to
+ * the emitter: later updates of the emitter do not reach it and it may outlive the emitter.
+ * A time-lapse, a cumulative-sky map or a time-averaged sky is one launch instead of one
+ * restaging and one pass over the rays per instant.
+ * Out of scope: per-ray wavelengths (their channel index is per lane, so a frame's record
+ * would no longer be wave-uniform), per-ray frame indices, sampling, AD, per-frame albedo /
+ * scales / aperture. */
+typedef struct sunsky_sequence sunsky_sequence;
+typedef struct sunsky_sequence_desc {
+    int count;        /* frames                       */
+    int variant;      /* sunsky_variant               */
+    int nb_channels;  /* 3 (RGB) / 11 (spectral)      */
+    int precision;    /* sunsky_precision             */
+    int device;       /* HIP device; -1: host-only    */
+} sunsky_sequence_desc;
+/* compute_sun_coordinates (sunsky.h:284-374), fp32 as the emitter's time/location mode
+ * evaluates it: the unit sun direction in the emitter's local frame (z up) for a date, a
+ * time and a place -- what turns a list of times into frame directions (to_world applied by
+ * the caller gives the world-space direction sunsky_sequence_create takes). */
+int sunsky_sun_coordinates(int year, int month, int day, float hour, float minute, float second,
+                           float latitude, float longitude, float timezone, float out[3]);
+/* Host-synchronous, like sunsky_emitter_create; on the emitter's device.  sun_dirs: count x 3
+ * host floats (normalised as the emitter's constructor does, sunsky.cpp:923); turbidity: count
+ * host floats, NULL = the emitter's; weights: count host floats, NULL = 1.  Errors
+ * (SUNSKY_ERROR_INVALID_VALUE): "Turbidity value %f is out of range [1, 10]" (sunsky.cpp:248),
+ * a zero or non-finite direction, a negative or non-finite weight, count < 1.  The frames'
+ * sky channels are staged by one kernel (one workgroup per frame) with the arithmetic of the
+ * emitter's own staging: frame k's channels are bit for bit those of a single emitter with
+ * that frame's parameters.  Over a host-only emitter (sunsky_emitter_create_host) the staging
+ * runs on the host and batch calls on the sequence fail, as they do on the emitter. */
+int sunsky_sequence_create(const sunsky_emitter *e, int count, const float *sun_dirs,
+                           const float *turbidity, const float *weights, sunsky_sequence **out);
+void sunsky_sequence_destroy(sunsky_sequence *seq);
+int sunsky_sequence_info(const sunsky_sequence *seq, sunsky_sequence_desc *out);
+int sunsky_sequence_set_precision(sunsky_sequence *seq, int precision);
+/* Frame k as staged, for inspection and tests (any output may be NULL): its local sun
+ * direction, weight, turbidity, nb_channels x 9 sky coefficients (SUNSKY_TABLE_SKY_PARAMS
+ * layout) and nb_channels sky radiances. */
+int sunsky_sequence_get_frame(const sunsky_sequence *seq, int k, float sun_dir_local[3], float *weight,
+                              float *turbidity, float *sky_params, float *sky_radiance);
+/* The weighted sum of eval(si) over the frames (wi = si.wi).  RGB: wavelengths_host = NULL,
+ * 3 planes.  Spectral: one host wavelength list broadcast to every ray, the
+ * sunsky_eval_spectral_broadcast layout (<= 32 wavelengths; out plane k = lambda[k]; an
+ * invalid wavelength gives 0).  A hot-path call. */
+int sunsky_sequence_eval(const sunsky_sequence *seq, sunsky_vec3_in wi, const float *wavelengths_host,
+                         int n_wavelengths, const uint8_t *active, size_t n, float *out,
+                         size_t out_stride, void *stream);
+/* sunsky_bake_latlong of the weighted sum: the same grid, planes and contract (successive
+ * bakes of one sequence are ordered through an event; not capturable). */
+int sunsky_sequence_bake_latlong(const sunsky_sequence *seq, int width, int height, float theta0,
+                                 float theta1, float phi0, float phi1, const float *wavelengths_host,
+                                 int n_wavelengths, float *out, size_t out_stride, void *stream);
 
 /* A caller of sample_direction / pdf_direction / eval: the sun-and-sky light a
  * smooth-diffuse point receives, gathered as the path integrator does at one vertex

@@ -363,6 +363,87 @@ private:
     sunsky_emitter* e_ = nullptr;
 };
 
+// ---------------------------------------------------------------- frame sequences
+// compute_sun_coordinates (sunsky.h:284-374): the local-frame (z up) sun direction of a date,
+// time and place (sunsky_sun_coordinates)
+struct SunPosition { float x, y, z; };
+inline SunPosition sun_coordinates(int year, int month, int day, float hour, float minute, float second, float latitude,
+                                   float longitude, float timezone) {
+    float d[3];
+    check(sunsky_sun_coordinates(year, month, day, hour, minute, second, latitude, longitude, timezone, d));
+    return SunPosition{d[0], d[1], d[2]};
+}
+
+// K frames (world sun direction, turbidity, weight) over a snapshot of an emitter
+// (sunsky_sequence_*): eval / bake_latlong return sum_k w_k eval_k in one launch.  The
+// sequence may outlive the emitter.
+class SunskySequence {
+public:
+    struct Frame {
+        float sun_dir_local[3];
+        float weight, turbidity;
+        std::vector<float> sky_params;     // nb_channels x 9
+        std::vector<float> sky_radiance;   // nb_channels
+    };
+    // sun_dirs: 3 floats per frame; turbidity / weights: one per frame, or empty (the
+    // emitter's turbidity / weight 1)
+    SunskySequence(const SunskyEmitter& emitter, const std::vector<float>& sun_dirs,
+                   const std::vector<float>& turbidity = {}, const std::vector<float>& weights = {}) {
+        const size_t count = sun_dirs.size() / 3;
+        if (sun_dirs.size() % 3 != 0 || (!turbidity.empty() && turbidity.size() != count) ||
+            (!weights.empty() && weights.size() != count))
+            throw Error(SUNSKY_ERROR_INVALID_VALUE, "sun_dirs needs 3 floats per frame, turbidity / weights one per frame");
+        check(sunsky_sequence_create(emitter.handle(), (int)count, sun_dirs.data(),
+                                     turbidity.empty() ? nullptr : turbidity.data(),
+                                     weights.empty() ? nullptr : weights.data(), &s_));
+    }
+    ~SunskySequence() { if (s_) sunsky_sequence_destroy(s_); }
+    SunskySequence(SunskySequence&& o) noexcept : s_(std::exchange(o.s_, nullptr)) {}
+    SunskySequence& operator=(SunskySequence&& o) noexcept {
+        if (this != &o) {
+            if (s_) sunsky_sequence_destroy(s_);
+            s_ = std::exchange(o.s_, nullptr);
+        }
+        return *this;
+    }
+    SunskySequence(const SunskySequence&) = delete;
+    SunskySequence& operator=(const SunskySequence&) = delete;
+
+    // sum_k w_k eval_k(si): RGB (no wavelengths, 3 planes) or one broadcast wavelength list
+    void eval(Vector3 wi, size_t n, SpectrumOut out, const std::vector<float>& wavelengths = {},
+              const uint8_t* active = nullptr, void* stream = nullptr) const {
+        check(sunsky_sequence_eval(s_, sunsky_vec3_in{wi.x, wi.y, wi.z}, wavelengths.empty() ? nullptr : wavelengths.data(),
+                                   (int)wavelengths.size(), active, n, out.data, out.stride ? out.stride : n, stream));
+    }
+    void bake_latlong(int width, int height, float theta0, float theta1, float phi0, float phi1, SpectrumOut out,
+                      const std::vector<float>& wavelengths = {}, void* stream = nullptr) const {
+        const size_t n = (size_t)width * (size_t)height;
+        check(sunsky_sequence_bake_latlong(s_, width, height, theta0, theta1, phi0, phi1,
+                                           wavelengths.empty() ? nullptr : wavelengths.data(), (int)wavelengths.size(),
+                                           out.data, out.stride ? out.stride : n, stream));
+    }
+    sunsky_sequence_desc info() const {
+        sunsky_sequence_desc d;
+        check(sunsky_sequence_info(s_, &d));
+        return d;
+    }
+    int count() const { return info().count; }
+    void set_precision(Precision p) { check(sunsky_sequence_set_precision(s_, (int)p)); }
+    Frame frame(int k) const {
+        const int nch = info().nb_channels;
+        Frame f;
+        f.sky_params.resize((size_t)nch * 9);
+        f.sky_radiance.resize(nch);
+        check(sunsky_sequence_get_frame(s_, k, f.sun_dir_local, &f.weight, &f.turbidity, f.sky_params.data(),
+                                        f.sky_radiance.data()));
+        return f;
+    }
+    const sunsky_sequence* handle() const { return s_; }
+
+private:
+    sunsky_sequence* s_ = nullptr;
+};
+
 // mi.hosek_sun_rad (sunsky_v.cpp:19): Hosek-Wilkie solar radiance, fp64; dataset nullptr = bundled pack
 inline double hosek_sun_rad(double turbidity, double wavelength, double elevation, double gamma,
                             const char* dataset = nullptr) {

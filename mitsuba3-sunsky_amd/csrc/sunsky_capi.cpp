@@ -116,7 +116,9 @@ void check_xform_form(hipModule_t mod, const std::string& path, bool want_identi
 //    MI355X (profiles/r01_v2_kbench_grid_sweep.log): RGB eval 64 (60.4 us vs 64.9 us at 16
 //    for 16M directions), spectral 64, sampling 64 (profiles/r01_v5_kbench.log,
 //    r01_v7_tune.log); sample_ray 32, from the sweep over 8/16/32/64
-//    (profiles/r03_v18_kbench_grid_ray_wavelengths.log); 16 where no sweep is recorded.
+//    (profiles/r03_v18_kbench_grid_ray_wavelengths.log); 16 where no sweep is recorded.  The
+//    sequence kernels (one ray per lane, bound by VALU issue, not memory) take 64: one step per
+//    lane up to 4M rays, where the cap only bounds the grid.
 //  * dir: the eval kernels are instantiated twice: eval(si) negates wi at compile time,
 //    eval_direction(ds) uses ds.d as is (name_dir_fast, name_dir_ref).
 //  * per: samples per work item: 4 consecutive directions per lane in the VEC = 4 kernels
@@ -155,6 +157,10 @@ void check_xform_form(hipModule_t mod, const std::string& path, bool want_identi
     X(DIRECT_CONDUCTOR_RGB, "sunsky_direct_conductor_rgb", 64, false, 1)                           \
     X(DIRECT_CONDUCTOR_SPEC, "sunsky_direct_conductor_spec", 64, false, 1)                         \
     X(DIRECT_CONDUCTOR_RAYS, "sunsky_direct_conductor_rays", 64, false, 1)                         \
+    X(SEQUENCE_EVAL_RGB, "sunsky_sequence_eval_rgb", 64, false, 1)                                 \
+    X(SEQUENCE_EVAL_SPEC, "sunsky_sequence_eval_spec", 64, false, 1)                               \
+    X(SEQUENCE_BAKE_RGB, "sunsky_sequence_bake_rgb", 64, false, 1)                                 \
+    X(SEQUENCE_BAKE_SPEC, "sunsky_sequence_bake_spec", 64, false, 1)                               \
     X(DEBUG_SUN_SEGMENTS, "sunsky_debug_sun_segments", 16, false, 1)
 
 #define X(id, name, wg, dir, per) K_##id,
@@ -183,6 +189,7 @@ struct DeviceModule {
     hipFunction_t latlong_tables = nullptr;                                     // bake_latlong
     hipFunction_t stage_radiance = nullptr, quad_points = nullptr, quad_finish = nullptr;   // parameters_changed
     hipFunction_t stage_tangent = nullptr;                                      // eval_jvp / eval_vjp tables
+    hipFunction_t stage_sequence = nullptr;                                     // sequence_create
     int cu_count = 256;
 };
 
@@ -223,6 +230,7 @@ DeviceModule* module_for_device(int dev) {
     get(&m->vjp_dir_spec, m->module, "sunsky_eval_vjp_dir_spec");
     get(&m->latlong_tables, m->module, "sunsky_latlong_tables");
     get(&m->stage_tangent, m->module, "sunsky_stage_tangent");
+    get(&m->stage_sequence, m->module, "sunsky_stage_sequence");
     get(&m->stage_radiance, m->module, "sunsky_stage_radiance");
     get(&m->quad_points, m->module, "sunsky_stage_quad_points");
     get(&m->quad_finish, m->module, "sunsky_stage_quad_finish");
@@ -258,6 +266,17 @@ void launch(hipFunction_t f, unsigned grid, hipStream_t stream, void** args, uns
 // 750 us at 5 and 745 us at 4 workgroups per CU, 806 us at 2; at one step per lane (16M)
 // neutral (profiles/r06_v8_nodes_occupancy_cold.log, r06_v7_ab_nodes_lds_cap.log).
 constexpr unsigned kNodesLdsCap = 32000;
+
+// Kernel k of code object `form` (1: identity to_world) and `precision` over n samples on
+// stream s.  dir: the eval_direction form (wo = d) of an eval kernel.
+void run_kernel(const DeviceModule* mod, int form, int precision, KernelId k, size_t n, void** args, hipStream_t s,
+                bool dir = false) {
+    const size_t per = (size_t)kKernels[k].per_item, items = (n + per - 1) / per;
+    const unsigned grid = grid_for(mod, k, items);
+    const bool multi_step = items > (size_t)grid * kBlock;
+    const auto& fns = dir ? mod->fn_dir : mod->fn;
+    launch(fns[form][precision][k], grid, s, args, k == K_EVAL_SPEC_NODES_V4 && multi_step ? kNodesLdsCap : 0u);
+}
 
 // The VEC = 4 kernels move 16 bytes per lane and plane (4 mask bytes).  How many of a batch's
 // n samples they can take: the multiple of 4 below n when every plane of `planes` is 16-byte
@@ -605,14 +624,121 @@ struct Launcher {
 
     // Kernel k over n samples.  dir: the eval_direction form (wo = d) of an eval kernel.
     void run(KernelId k, size_t n, void** args, bool dir = false) const {
-        const size_t per = (size_t)kKernels[k].per_item, items = (n + per - 1) / per;
-        const unsigned grid = grid_for(e->mod, k, items);
-        const bool multi_step = items > (size_t)grid * kBlock;
-        const auto& fns = dir ? e->mod->fn_dir : e->mod->fn;
-        launch(fns[e->xform_form(s)][e->precision][k], grid, s, args,
-               k == K_EVAL_SPEC_NODES_V4 && multi_step ? kNodesLdsCap : 0u);
+        run_kernel(e->mod, e->xform_form(s), e->precision, k, n, args, s, dir);
     }
 };
+
+// ---------------------------------------------------------------- sequences
+// K frames over a snapshot of one emitter (sunsky_amd.h, "frame sequences").  The object
+// owns everything its kernels read: a copy of the emitter's state block (geometry, scales,
+// aperture, segment thresholds), the frame records, the raw sun dataset the disc lanes lerp
+// from, and the limb-darkening table.  Nothing points back to the emitter.
+struct sunsky_sequence {
+    SunskyKArgs kargs;                       // the snapshot (host); sun_ld -> d_sun_ld on the device
+    int count = 0, nch = 0, variant = 0;
+    int precision = SUNSKY_PRECISION_FAST;
+    int device = -1;                         // -1: host-only (no batch calls)
+    DeviceModule* mod = nullptr;
+    std::vector<unsigned char> records;      // SeqFrame<nch>[count], staged (host mirror: get_frame)
+    size_t rec_bytes = 0;
+    int sun_block = 0;
+    SunskyKArgs* d_state = nullptr;
+    void* d_frames = nullptr;
+    float* d_sun_rad = nullptr;
+    float* d_sun_ld = nullptr;
+    mutable float* d_bake = nullptr;         // bake_latlong angle tables, ordered as the emitter's
+    mutable size_t bake_cap = 0;
+    mutable hipEvent_t bake_done = nullptr;
+
+    void require_device() const {
+        if (!mod) throw std::invalid_argument("host-only sequence (over a sunsky_emitter_create_host emitter) cannot launch kernels");
+    }
+    // The snapshot never changes, so an identity to_world takes the identity code object under
+    // capture too (SUNSKY_AMD_GENERAL_XFORM=1: the general one always)
+    int xform_form() const {
+        const char* g = std::getenv("SUNSKY_AMD_GENERAL_XFORM");
+        return kargs.identity_xform && !(g && g[0] == '1') ? 1 : 0;
+    }
+    SeqArgs args() const { return SeqArgs{d_frames, d_sun_rad, count, sun_block}; }
+
+    ~sunsky_sequence() {
+        if (device < 0) return;
+        int cur = -1;
+        if (hipGetDevice(&cur) == hipSuccess && cur != device) (void)hipSetDevice(device);
+        (void)hipDeviceSynchronize();   // launches in flight may still read the records
+        for (void* p : {(void*)d_state, d_frames, (void*)d_sun_rad, (void*)d_sun_ld, (void*)d_bake})
+            if (p) (void)hipFree(p);
+        if (bake_done) (void)hipEventDestroy(bake_done);
+        if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
+    }
+};
+
+namespace {
+
+// The header of frame k's record (the same for every channel count)
+SeqFrame<1>* seq_header(sunsky_sequence* q, int k) {
+    return reinterpret_cast<SeqFrame<1>*>(q->records.data() + (size_t)k * q->rec_bytes);
+}
+const SeqFrame<1>* seq_header(const sunsky_sequence* q, int k) {
+    return reinterpret_cast<const SeqFrame<1>*>(q->records.data() + (size_t)k * q->rec_bytes);
+}
+const SkyChannel* seq_sky(const sunsky_sequence* q, int k) {
+    return reinterpret_cast<const SkyChannel*>(q->records.data() + (size_t)k * q->rec_bytes + kSeqFrameHeader +
+                                               (size_t)q->nch * sizeof(FastChannel));
+}
+
+// Validation and the per-frame geometry staging from the parent's state: the local sun
+// direction as the emitter's constructor forms it (normalised, then to_local; sunsky.cpp:
+// 923, 176), and the RadianceStage scalars of (its elevation, the frame's turbidity).
+void seq_fill_headers(sunsky_sequence* q, const SunskyModel& model, const float* dirs, const float* turbidity,
+                      const float* weights) {
+    for (int k = 0; k < q->count; ++k) {
+        const float T = turbidity ? turbidity[k] : model.turbidity();
+        if (!(T >= 1.f && T <= 10.f)) {
+            char buf[128];
+            std::snprintf(buf, sizeof(buf), "Turbidity value %f is out of range [1, 10]", T);
+            throw std::invalid_argument(std::string(buf) + " (frame " + std::to_string(k) + ")");
+        }
+        const float w = weights ? weights[k] : 1.f;
+        if (!std::isfinite(w) || w < 0.f)
+            throw std::invalid_argument("frame " + std::to_string(k) + ": the weight must be finite and >= 0");
+        const float3_ d = mk3(dirs[3 * k], dirs[3 * k + 1], dirs[3 * k + 2]);
+        const float len2 = dot3(d, d);
+        if (!std::isfinite(len2) || !(len2 > 0.f))
+            throw std::invalid_argument("frame " + std::to_string(k) + ": the sun direction must be finite and non-zero");
+        const float inv = 1.f / sqrtf(len2);
+        const float3_ l = xform_vec(q->kargs.to_local, mk3(d.x * inv, d.y * inv, d.z * inv));
+        const RadianceStage rs = radiance_stage_for(unit_angle_z(l), T);
+        SeqFrame<1>* h = seq_header(q, k);
+        h->sun_n[0] = l.x; h->sun_n[1] = l.y; h->sun_n[2] = l.z;
+        h->weight = w;
+        h->t_rem = rs.t_rem;
+        h->t_low = rs.t_low;
+        h->t_high = rs.t_high;
+        h->turbidity = T;
+        h->x = rs.x;
+        h->in_range = rs.in_range;
+    }
+}
+
+// sunsky_stage_sequence on the host (host-only sequences): the same functions per entry
+void seq_stage_host(sunsky_sequence* q, const SunskyModel& model, float sky_scale) {
+    const int nch = q->nch, np = nch * kNbSkyParams;
+    const std::vector<float>& alb = model.albedo();
+    std::vector<float> p(np), r(nch);
+    for (int k = 0; k < q->count; ++k) {
+        const SeqFrame<1>* h = seq_header(q, k);
+        const RadianceStage rs = {h->x, h->t_rem, h->t_low, h->t_high, h->in_range};
+        for (int e = 0; e < np; ++e) p[e] = radiance_param(model.sky_params_ds().data(), np, e, rs, alb[e / kNbSkyParams]);
+        for (int e = 0; e < nch; ++e) r[e] = radiance_param(model.sky_rad_ds().data(), nch, e, rs, alb[e]);
+        unsigned char* rec = q->records.data() + (size_t)k * q->rec_bytes;
+        FastChannel* fast = reinterpret_cast<FastChannel*>(rec + kSeqFrameHeader);
+        SkyChannel* sky = reinterpret_cast<SkyChannel*>(rec + kSeqFrameHeader + (size_t)nch * sizeof(FastChannel));
+        for (int c = 0; c < nch; ++c) fold_channel(&p[c * kNbSkyParams], r[c], q->variant, sky_scale, &sky[c], &fast[c]);
+    }
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -1322,6 +1448,199 @@ int sunsky_bake_latlong(const sunsky_emitter* e, int width, int height, float th
             lc.run(K_BAKE_SPEC, n, args);
         }
         hip_check(hipEventRecord(e->bake_done, s), "hipEventRecord");
+    });
+}
+
+// ---------------------------------------------------------------- frame sequences
+int sunsky_sun_coordinates(int year, int month, int day, float hour, float minute, float second, float latitude,
+                           float longitude, float timezone, float out[3]) {
+    if (!out) return fail(SUNSKY_ERROR_INVALID_VALUE, "null output pointer");
+    DateTime t;
+    t.year = year; t.month = month; t.day = day; t.hour = hour; t.minute = minute; t.second = second;
+    Location l;
+    l.latitude = latitude; l.longitude = longitude; l.timezone = timezone;
+    compute_sun_coordinates(t, l, out);
+    return SUNSKY_OK;
+}
+
+int sunsky_sequence_create(const sunsky_emitter* e, int count, const float* sun_dirs, const float* turbidity,
+                           const float* weights, sunsky_sequence** out) {
+    SUNSKY_PHASE("InitScene", "sequence_create");
+    if (!e || !out) return fail(SUNSKY_ERROR_INVALID_VALUE, "null emitter / output pointer");
+    *out = nullptr;
+    if (count < 1) return fail(SUNSKY_ERROR_INVALID_VALUE, "a sequence needs at least one frame (count >= 1)");
+    if (!sun_dirs) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sun direction array");
+    return guarded([&] {
+        std::unique_ptr<sunsky_sequence> q(new sunsky_sequence());
+        const SunskyModel& model = *e->model;
+        q->kargs = e->kargs;
+        q->kargs.sun_table = nullptr;   // no per-frame sun table: the disc lanes lerp the raw dataset
+        q->kargs.sun_ld = nullptr;
+        q->count = count;
+        q->nch = model.nch();
+        q->variant = model.variant();
+        q->precision = e->precision;
+        q->sun_block = q->variant == kSpectral ? kSunSpecTableSize : kSunRgbTableSize;
+        q->rec_bytes = kSeqFrameHeader + (size_t)q->nch * (sizeof(FastChannel) + sizeof(SkyChannel));
+        q->records.assign((size_t)count * q->rec_bytes, 0);
+        seq_fill_headers(q.get(), model, sun_dirs, turbidity, weights);
+        if (e->device < 0) {
+            seq_stage_host(q.get(), model, q->kargs.sky_scale);
+            *out = q.release();
+            return;
+        }
+        DeviceScope g(e->device);
+        q->mod = e->mod;
+        // from here on the destructor frees what was allocated
+        q->device = e->device;
+        const std::vector<float>& su = model.sun_rad_ds();
+        const std::vector<float>& ld = model.sun_ld();
+        hip_check(hipMalloc(&q->d_frames, q->records.size()), "hipMalloc");
+        hip_check(hipMalloc(&q->d_sun_rad, sizeof(float) * su.size()), "hipMalloc");
+        hip_check(hipMalloc(&q->d_sun_ld, sizeof(float) * kNbWavelengths * kNbSunLdParams), "hipMalloc");
+        hip_check(hipMalloc(&q->d_state, sizeof(SunskyKArgs)), "hipMalloc");
+        hip_check(hipMemcpy(q->d_frames, q->records.data(), q->records.size(), hipMemcpyHostToDevice), "hipMemcpy");
+        hip_check(hipMemcpy(q->d_sun_rad, su.data(), sizeof(float) * su.size(), hipMemcpyHostToDevice), "hipMemcpy");
+        hip_check(hipMemset(q->d_sun_ld, 0, sizeof(float) * kNbWavelengths * kNbSunLdParams), "hipMemset");
+        hip_check(hipMemcpy(q->d_sun_ld, ld.data(), sizeof(float) * std::min<size_t>(ld.size(), kNbWavelengths * kNbSunLdParams),
+                            hipMemcpyHostToDevice), "hipMemcpy");
+        q->kargs.sun_ld = q->d_sun_ld;
+        hip_check(hipMemcpy(q->d_state, &q->kargs, sizeof(SunskyKArgs), hipMemcpyHostToDevice), "hipMemcpy");
+        SeqStageArgs A;
+        std::memset(&A, 0, sizeof(A));
+        A.frames = q->d_frames;
+        A.sky_params_ds = e->d_sky_params_ds;
+        A.sky_rad_ds = e->d_sky_rad_ds;
+        const std::vector<float>& alb = model.albedo();
+        for (int c = 0; c < q->nch; ++c) A.albedo[c] = alb[c];
+        A.nch = q->nch;
+        A.variant = q->variant;
+        A.count = count;
+        A.sky_scale = q->kargs.sky_scale;
+        void* sargs[] = {&A};
+        hip_check(hipModuleLaunchKernel(q->mod->stage_sequence, (unsigned)std::min(count, 65535), 1, 1, 256, 1, 1, 0, nullptr,
+                                        sargs, nullptr), "hipModuleLaunchKernel(sunsky_stage_sequence)");
+        hip_check(hipStreamSynchronize(nullptr), "hipStreamSynchronize");
+        hip_check(hipMemcpy(q->records.data(), q->d_frames, q->records.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+        *out = q.release();
+    });
+}
+
+void sunsky_sequence_destroy(sunsky_sequence* seq) { delete seq; }
+
+int sunsky_sequence_info(const sunsky_sequence* seq, sunsky_sequence_desc* out) {
+    if (!seq || !out) return fail(SUNSKY_ERROR_INVALID_VALUE, "null argument");
+    out->count = seq->count;
+    out->variant = seq->variant;
+    out->nb_channels = seq->nch;
+    out->precision = seq->precision;
+    out->device = seq->device;
+    return SUNSKY_OK;
+}
+
+int sunsky_sequence_set_precision(sunsky_sequence* seq, int precision) {
+    if (!seq || (precision != SUNSKY_PRECISION_FAST && precision != SUNSKY_PRECISION_REFERENCE))
+        return fail(SUNSKY_ERROR_INVALID_VALUE, "invalid precision mode");
+    seq->precision = precision;
+    return SUNSKY_OK;
+}
+
+int sunsky_sequence_get_frame(const sunsky_sequence* seq, int k, float sun_dir_local[3], float* weight, float* turbidity,
+                              float* sky_params, float* sky_radiance) {
+    if (!seq) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sequence");
+    if (k < 0 || k >= seq->count) return fail(SUNSKY_ERROR_INVALID_VALUE, "frame index out of range");
+    const SeqFrame<1>* h = seq_header(seq, k);
+    const SkyChannel* sky = seq_sky(seq, k);
+    if (sun_dir_local) std::memcpy(sun_dir_local, h->sun_n, 3 * sizeof(float));
+    if (weight) *weight = h->weight;
+    if (turbidity) *turbidity = h->turbidity;
+    for (int c = 0; c < seq->nch; ++c) {
+        const SkyChannel& ch = sky[c];
+        const float p[kNbSkyParams] = {ch.A, ch.B, ch.C, ch.D, ch.E, ch.F, ch.G, ch.H, ch.I};
+        if (sky_params) std::memcpy(sky_params + (size_t)c * kNbSkyParams, p, sizeof(p));
+        if (sky_radiance) sky_radiance[c] = ch.rad;
+    }
+    return SUNSKY_OK;
+}
+
+int sunsky_sequence_eval(const sunsky_sequence* seq, sunsky_vec3_in w, const float* lam_host, int m,
+                         const uint8_t* active, size_t n, float* out, size_t ostride, void* stream) {
+    SUNSKY_PHASE("EndpointEvaluate", "sequence_eval");
+    if (!seq) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sequence");
+    const bool spec = seq->variant == kSpectral;
+    if (spec && (!lam_host || m < 1 || m > kMaxBroadcastLambda))
+        return fail(SUNSKY_ERROR_INVALID_VALUE, "1..32 broadcast wavelengths required for a spectral sequence");
+    if (!spec && lam_host && m) return fail(SUNSKY_ERROR_INVALID_VALUE, "an RGB sequence takes no wavelengths");
+    if (n == 0) return SUNSKY_OK;
+    if (!w.x || !w.y || !w.z || !out) return fail(SUNSKY_ERROR_INVALID_VALUE, "null ray / output pointer");
+    if ((spec ? m : 3) > 1 && ostride < n) return fail(SUNSKY_ERROR_INVALID_VALUE, "out_stride < n");
+    return guarded([&] {
+        seq->require_device();
+        DeviceScope g(seq->device);
+        const SunskyKArgs* K = seq->d_state;
+        SeqArgs A = seq->args();
+        if (!spec) {
+            void* args[] = {&K, &A, (void*)&w.x, (void*)&w.y, (void*)&w.z, &active, &n, &out, &ostride};
+            run_kernel(seq->mod, seq->xform_form(), seq->precision, K_SEQUENCE_EVAL_RGB, n, args, (hipStream_t)stream);
+        } else {
+            LambdaSet L = make_lambda_set(lam_host, m);
+            void* args[] = {&K, &A, &L, (void*)&w.x, (void*)&w.y, (void*)&w.z, &active, &n, &out, &ostride};
+            run_kernel(seq->mod, seq->xform_form(), seq->precision, K_SEQUENCE_EVAL_SPEC, n, args, (hipStream_t)stream);
+        }
+    });
+}
+
+int sunsky_sequence_bake_latlong(const sunsky_sequence* seq, int width, int height, float theta0, float theta1,
+                                 float phi0, float phi1, const float* lam_host, int m, float* out, size_t ostride,
+                                 void* stream) {
+    SUNSKY_PHASE("EndpointEvaluate", "sequence_bake_latlong");
+    if (!seq) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sequence");
+    if (width < 1 || height < 1) return fail(SUNSKY_ERROR_INVALID_VALUE, "image size must be >= 1 x 1");
+    if ((int64_t)width * height >= (int64_t)1 << 31) return fail(SUNSKY_ERROR_INVALID_VALUE, "image larger than 2^31 pixels");
+    const bool spec = seq->variant == kSpectral;
+    if (spec && (!lam_host || m < 1 || m > kMaxBroadcastLambda))
+        return fail(SUNSKY_ERROR_INVALID_VALUE, "1..32 wavelengths required for a spectral bake");
+    if (!spec && lam_host && m) return fail(SUNSKY_ERROR_INVALID_VALUE, "RGB bake takes no wavelengths");
+    const size_t n = (size_t)width * (size_t)height;
+    if (!out) return fail(SUNSKY_ERROR_INVALID_VALUE, "null output pointer");
+    if (ostride < n) return fail(SUNSKY_ERROR_INVALID_VALUE, "out_stride < width * height");
+    LatLong G = {width, height, theta0, height > 1 ? (theta1 - theta0) / (float)(height - 1) : 0.f,
+                 phi0, width > 1 ? (phi1 - phi0) / (float)(width - 1) : 0.f, nullptr};
+    return guarded([&] {
+        seq->require_device();
+        DeviceScope g(seq->device);
+        hipStream_t s = (hipStream_t)stream;
+        // the angle tables are per sequence, ordered between bakes as sunsky_bake_latlong's
+        const size_t need = 2 * (size_t)width + 2 * (size_t)height;
+        const bool had_bake = seq->bake_done != nullptr;
+        if (!had_bake) hip_check(hipEventCreateWithFlags(&seq->bake_done, hipEventDisableTiming), "hipEventCreate");
+        else hip_check(hipStreamWaitEvent(s, seq->bake_done, 0), "hipStreamWaitEvent");
+        if (seq->bake_cap < need) {
+            if (had_bake) hip_check(hipEventSynchronize(seq->bake_done), "hipEventSynchronize");
+            if (seq->d_bake) hip_check(hipFree(seq->d_bake), "hipFree");
+            seq->d_bake = nullptr;
+            seq->bake_cap = 0;
+            hip_check(hipMalloc(&seq->d_bake, sizeof(float) * need), "hipMalloc");
+            seq->bake_cap = need;
+        }
+        float* tab = seq->d_bake;
+        G.tab = tab;
+        {
+            void* targs[] = {&G, &tab};
+            const unsigned tg = (unsigned)((std::max(width, height) + kBlock - 1) / kBlock);
+            launch(seq->mod->latlong_tables, tg, s, targs);
+        }
+        const SunskyKArgs* K = seq->d_state;
+        SeqArgs A = seq->args();
+        if (!spec) {
+            void* args[] = {&K, &A, &G, &out, &ostride};
+            run_kernel(seq->mod, seq->xform_form(), seq->precision, K_SEQUENCE_BAKE_RGB, n, args, s);
+        } else {
+            LambdaSet L = make_lambda_set(lam_host, m);
+            void* args[] = {&K, &A, &G, &L, &out, &ostride};
+            run_kernel(seq->mod, seq->xform_form(), seq->precision, K_SEQUENCE_BAKE_SPEC, n, args, s);
+        }
+        hip_check(hipEventRecord(seq->bake_done, s), "hipEventRecord");
     });
 }
 

@@ -64,4 +64,51 @@ struct QuadArgs {
 };
 static_assert(sizeof(QuadArgs) == 104 && offsetof(QuadArgs, status) == 96, "QuadArgs layout");
 
+// ---------------------------------------------------------------- frame sequences
+// One frame of a sunsky_sequence in device memory (NCH = 3 RGB, 11 spectral): what differs
+// between the frames of one emitter.  The host fills the header (and zeroes the channels);
+// sunsky_stage_sequence writes the channels in place from the header's RadianceStage scalars
+// (host-only sequences run the same functions on the host).  The accumulate kernels read a
+// record with one address per wave: every block is 16-byte aligned for wide scalar loads.
+template <int NCH>
+struct alignas(16) SeqFrame {
+    float sun_n[3];            // local sun direction (m_local_sun_frame.n of the frame's emitter)
+    float weight;
+    float t_rem;               // turbidity lerp scalars (RadianceStage): the disc lanes' sun_param
+    int t_low, t_high;
+    float turbidity;
+    float x;                   // cbrt(2 eta / pi) of the frame's sun elevation (staging only)
+    int in_range;              // 0 <= eta <= pi / 2 (staging only)
+    float pad[2];
+    FastChannel fast[NCH];     // FAST kernels
+    SkyChannel sky[NCH];       // reference kernels, get_frame
+};
+constexpr size_t kSeqFrameHeader = 48;
+static_assert(sizeof(SkyChannel) == 64, "SkyChannel record stride");
+static_assert(sizeof(SeqFrame<3>) == kSeqFrameHeader + 3 * 112 && sizeof(SeqFrame<kNbWavelengths>) == kSeqFrameHeader + 11 * 112,
+              "SeqFrame layout");
+static_assert(offsetof(SeqFrame<3>, weight) == 12 && offsetof(SeqFrame<3>, t_rem) == 16 &&
+              offsetof(SeqFrame<3>, x) == 32 && offsetof(SeqFrame<3>, fast) == kSeqFrameHeader &&
+              offsetof(SeqFrame<3>, sky) == kSeqFrameHeader + 3 * 48 &&
+              offsetof(SeqFrame<kNbWavelengths>, sky) == kSeqFrameHeader + 11 * 48, "SeqFrame layout");
+
+// sunsky_stage_sequence: one workgroup per frame
+struct SeqStageArgs {
+    void* frames;                  // SeqFrame<nch>[count], headers filled
+    const float* sky_params_ds;    // the parent emitter's device datasets (read at creation only)
+    const float* sky_rad_ds;
+    float albedo[kNbWavelengths];
+    int nch, variant, count;
+    float sky_scale;
+};
+static_assert(sizeof(SeqStageArgs) == 24 + 4 * kNbWavelengths + 16 + 4, "SeqStageArgs layout");
+
+// The accumulate kernels' view of a sequence
+struct SeqArgs {
+    const void* frames;            // SeqFrame<nch>[count]
+    const float* sun_rad_ds;       // raw sun dataset (10 turbidities x sun block), device
+    int count, sun_block;
+};
+static_assert(sizeof(SeqArgs) == 24, "SeqArgs layout");
+
 }  // namespace sunsky

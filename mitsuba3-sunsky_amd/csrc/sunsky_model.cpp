@@ -332,16 +332,18 @@ void SunskyModel::update_angles(const float l[3]) {
 }
 
 // Scalars of the radiance / sun-table staging for the current (turbidity, eta)
-RadianceStage SunskyModel::radiance_stage() const {
-    const float eta = 0.5f * kPi - k_.sun_theta;
+RadianceStage radiance_stage_for(float sun_theta, float turbidity) {
+    const float eta = 0.5f * kPi - sun_theta;
     RadianceStage r;
     r.x = cbrtf(2.f * kInvPi * eta);
-    r.t_high = (int)floorf(turbidity_);
+    r.t_high = (int)floorf(turbidity);
     r.t_low = r.t_high - 1;
-    r.t_rem = turbidity_ - (float)r.t_high;
+    r.t_rem = turbidity - (float)r.t_high;
     r.in_range = (0.f <= eta) && (eta <= 0.5f * kPi);
     return r;
 }
+
+RadianceStage SunskyModel::radiance_stage() const { return radiance_stage_for(k_.sun_theta, turbidity_); }
 
 // compute_radiance_params x2 + compute_sun_params + channel folding (sunsky.h:158-231,
 // 404-419): the part of parameters_changed a GPU emitter runs on the device instead.

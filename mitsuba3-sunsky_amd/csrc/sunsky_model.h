@@ -19,6 +19,10 @@ struct Location { float latitude = 35.6894f, longitude = 139.6917f, timezone = 9
 
 // compute_sun_coordinates, sunsky.h:284-374 (fp32, Int32 Julian-day arithmetic)
 void compute_sun_coordinates(const DateTime& t, const Location& l, float out[3]);
+// Scalars of the radiance / sun-table staging (sunsky.h:158-231, 404-419) for a sun at polar
+// angle sun_theta (local frame) and a turbidity: the emitter's own staging and every frame
+// of a sequence compute them here, so a frame's staged channels are its emitter's bits.
+RadianceStage radiance_stage_for(float sun_theta, float turbidity);
 // quad::gauss_legendre, quad.h:27-86 (fp64 nodes/weights)
 void gauss_legendre(int n, std::vector<double>* nodes, std::vector<double>* weights);
 

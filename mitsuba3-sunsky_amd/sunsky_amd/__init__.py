@@ -6,7 +6,8 @@ from .emitter import (SunskyEmitter, Parameters, load_dict, array_from_file, arr
 from .records import (SurfaceInteraction3f, Interaction3f, DirectionSample3f, Ray3f,  # noqa: F401
                       ScalarBoundingBox3f)
 from .autograd import eval_wi  # noqa: F401
+from .sequence import SunskySequence, sun_coordinates  # noqa: F401
 
-__all__ = ["SunskyEmitter", "Parameters", "load_dict", "array_from_file", "array_to_file",
+__all__ = ["SunskySequence", "sun_coordinates","SunskyEmitter", "Parameters", "load_dict", "array_from_file", "array_to_file",
            "default_dataset_path", "hosek_sun_rad", "SurfaceInteraction3f", "Interaction3f", "DirectionSample3f", "Ray3f",
            "ScalarBoundingBox3f", "lib", "declared_functions", "eval_wi"]

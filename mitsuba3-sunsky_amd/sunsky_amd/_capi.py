@@ -52,6 +52,11 @@ class Info(C.Structure):
     ]
 
 
+class SequenceDesc(C.Structure):
+    _fields_ = [("count", C.c_int), ("variant", C.c_int), ("nb_channels", C.c_int), ("precision", C.c_int),
+                ("device", C.c_int)]
+
+
 _SIGS = {
     "sunsky_abi_version": (C.c_int, []),
     "sunsky_last_error": (C.c_char_p, []),
@@ -92,6 +97,16 @@ _SIGS = {
                                   vp, vp, C.c_size_t, vp]),
     "sunsky_bake_latlong": (C.c_int, [vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, c_float_p,
                                       C.c_int, vp, C.c_size_t, vp]),
+    "sunsky_sun_coordinates": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
+                                         C.c_float, C.c_float, c_float_p]),
+    "sunsky_sequence_create": (C.c_int, [vp, C.c_int, c_float_p, c_float_p, c_float_p, C.POINTER(vp)]),
+    "sunsky_sequence_destroy": (None, [vp]),
+    "sunsky_sequence_info": (C.c_int, [vp, C.POINTER(SequenceDesc)]),
+    "sunsky_sequence_set_precision": (C.c_int, [vp, C.c_int]),
+    "sunsky_sequence_get_frame": (C.c_int, [vp, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p]),
+    "sunsky_sequence_eval": (C.c_int, [vp, Vec3In, c_float_p, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp]),
+    "sunsky_sequence_bake_latlong": (C.c_int, [vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
+                                               c_float_p, C.c_int, vp, C.c_size_t, vp]),
     "sunsky_direct_diffuse": (C.c_int, [vp, Vec3In, vp, vp, C.c_int, C.c_size_t, C.c_uint32, C.c_uint32,
                                         vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp]),
     "sunsky_direct_diffuse_rays": (C.c_int, [vp, Vec3In, C.c_uint32, C.c_uint32, C.c_size_t, Vec3Out, Vec3Out,

@@ -1,0 +1,153 @@
+"""Weighted frame sequences over one emitter (sunsky_sequence_*, include/sunsky_amd.h):
+out = sum_k w_k eval_k(wi) for K sun directions / turbidities in one launch -- a time-lapse,
+a cumulative-sky map, a time-averaged sky.  The sequence is a snapshot of the emitter at
+creation; it keeps no reference to it.
+"""
+import ctypes as C
+import datetime
+import math
+
+import numpy as np
+import torch
+
+from . import _capi
+from ._capi import Vec3In, check, lib
+from .emitter import SunskyEmitter, _PRECISION, _fa, _ptr
+
+
+def sun_coordinates(year, month, day, hour, minute=0.0, second=0.0, latitude=35.6894, longitude=139.6917,
+                    timezone=9.0):
+    """compute_sun_coordinates (sunsky.h:284-374) in fp32, as the emitter's time/location mode
+    evaluates it: the unit sun direction in the emitter's local frame (z up)."""
+    out = (C.c_float * 3)()
+    check(lib().sunsky_sun_coordinates(int(year), int(month), int(day), float(hour), float(minute), float(second),
+                                       float(latitude), float(longitude), float(timezone), out))
+    return np.array(out, dtype=np.float32)
+
+
+def _time_fields(t):
+    if isinstance(t, datetime.datetime):
+        return t.year, t.month, t.day, float(t.hour), float(t.minute), t.second + t.microsecond * 1e-6
+    f = tuple(t)
+    if not 4 <= len(f) <= 6:
+        raise ValueError("a time is a datetime or (year, month, day, hour[, minute[, second]])")
+    return f + (0.0,) * (6 - len(f))
+
+
+class SunskySequence:
+    """K frames (sun direction, turbidity, weight) over a snapshot of `em`.
+
+    sun_directions -- (K, 3) world-space directions (normalised like the emitter's sun_direction)
+    turbidity      -- K values in [1, 10], a scalar, or None (the emitter's)
+    weights        -- K finite values >= 0, or None (1)
+    """
+
+    def __init__(self, em, sun_directions, turbidity=None, weights=None):
+        self._h = None
+        d = np.ascontiguousarray(np.asarray(sun_directions, dtype=np.float32))
+        if d.ndim != 2 or d.shape[1] != 3:
+            raise ValueError("sun_directions must have shape (K, 3)")
+        k = d.shape[0]
+
+        def per_frame(v, name):
+            if v is None:
+                return None
+            a = np.asarray(v, dtype=np.float32)
+            if a.ndim == 0:
+                a = np.full(k, a, dtype=np.float32)
+            if a.shape != (k,):
+                raise ValueError(f"{name} must have {k} values (one per frame), got shape {a.shape}")
+            return _fa(a.tolist())
+
+        t, w = per_frame(turbidity, "turbidity"), per_frame(weights, "weights")
+        self.device = em.device
+        self.variant, self.is_spectral = em.variant, em.is_spectral
+        h = C.c_void_p()
+        check(lib().sunsky_sequence_create(em._h, k, _fa(d.reshape(-1).tolist()), t, w, C.byref(h)))
+        self._h = h
+
+    @classmethod
+    def from_times(cls, em, times, latitude=35.6894, longitude=139.6917, timezone=9.0, turbidity=None, weights=None):
+        """Frames at the sun positions of `times` (datetimes or (year, month, day, hour[, minute[,
+        second]]) tuples) at one place, through sunsky_sun_coordinates and the emitter's to_world.
+        Night hours are valid frames (a sun below the horizon contributes no sky)."""
+        m = np.asarray(em.get_param("to_world"), dtype=np.float32)[:3, :3]
+        dirs = [m @ sun_coordinates(*_time_fields(t), latitude=latitude, longitude=longitude, timezone=timezone)
+                for t in times]
+        return cls(em, np.asarray(dirs, dtype=np.float32).reshape(-1, 3), turbidity, weights)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            self._h = None
+            try:
+                lib().sunsky_sequence_destroy(h)
+            except Exception:   # interpreter shutdown: the library may already be gone
+                pass
+
+    def __len__(self):
+        return self.info()["count"]
+
+    def info(self):
+        d = _capi.SequenceDesc()
+        check(lib().sunsky_sequence_info(self._h, C.byref(d)))
+        return {"count": d.count, "variant": d.variant, "nb_channels": d.nb_channels,
+                "precision": "fast" if d.precision == _capi.PRECISION_FAST else "reference", "device": d.device}
+
+    def set_precision(self, precision):
+        check(lib().sunsky_sequence_set_precision(self._h, _PRECISION[precision]))
+
+    def frame(self, k):
+        """Frame k as staged: local sun direction, weight, turbidity, (nch, 9) sky coefficients and
+        nch sky radiances (the layout of table("sky_params") / table("sky_radiance"))."""
+        nch = self.info()["nb_channels"]
+        sd, w, t = (C.c_float * 3)(), C.c_float(), C.c_float()
+        sp, sr = (C.c_float * (nch * 9))(), (C.c_float * nch)()
+        check(lib().sunsky_sequence_get_frame(self._h, int(k), sd, C.byref(w), C.byref(t), sp, sr))
+        return {"sun_dir_local": np.array(sd, dtype=np.float32), "weight": w.value, "turbidity": t.value,
+                "sky_params": np.array(sp, dtype=np.float32).reshape(nch, 9),
+                "sky_radiance": np.array(sr, dtype=np.float32)}
+
+    def _stream(self):
+        if self.device is None:
+            return C.c_void_p()
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _lambda(self, wavelengths, what):
+        if not self.is_spectral:
+            if wavelengths is not None:
+                raise ValueError(f"an RGB {what} takes no wavelengths")
+            return 3, None, 0
+        if wavelengths is None:
+            raise ValueError(f"a spectral {what} needs a wavelength list")
+        lam = [float(x) for x in np.atleast_1d(np.asarray(wavelengths, dtype=np.float32))]
+        return len(lam), _fa(lam), len(lam)
+
+    def eval(self, si_or_wi, wavelengths=None, active=None, out=None):
+        """sum_k w_k eval_k(si) -> (3, n) RGB, or (m, n) for one wavelength list broadcast to every
+        ray (spectral).  si_or_wi: a SurfaceInteraction3f or a (3, n) wi tensor."""
+        if self.device is None:
+            raise ValueError("host-only sequence (over a host-only emitter) cannot launch kernels")
+        wi = getattr(si_or_wi, "wi", si_or_wi)
+        wi, vin = SunskyEmitter._vec_in(self, wi)
+        n = wi.shape[1]
+        k, lam_p, m = self._lambda(wavelengths, "sequence eval")
+        out = SunskyEmitter._out(self, out, (k, n), row_stride_ok=True)
+        mask = SunskyEmitter._mask(self, active, n)
+        check(lib().sunsky_sequence_eval(self._h, vin, lam_p, m, _ptr(mask), n, _ptr(out), out.stride(0), self._stream()))
+        return out
+
+    def bake_latlong(self, width, height, theta=(0.0, math.pi), phi=(0.0, 2 * math.pi), wavelengths=None, out=None):
+        """Lat-long map of the weighted sum (sunsky_sequence_bake_latlong): (C, height, width), the
+        grid of SunskyEmitter.bake_latlong."""
+        if self.device is None:
+            raise ValueError("host-only sequence (over a host-only emitter) cannot launch kernels")
+        k, lam_p, m = self._lambda(wavelengths, "sequence bake")
+        out = SunskyEmitter._out(self, out, (k, height, width))
+        check(lib().sunsky_sequence_bake_latlong(self._h, width, height, float(theta[0]), float(theta[1]),
+                                                 float(phi[0]), float(phi[1]), lam_p, m, _ptr(out), height * width,
+                                                 self._stream()))
+        return out
+
+    # SunskyEmitter's tensor helpers read only self.device
+    _f32 = SunskyEmitter._f32

@@ -1,0 +1,96 @@
+"""Frame-sequence timing: one sequence.eval against the loop a user writes without it.
+
+Workload: RGB, FAST, n = 2^21 upper-hemisphere directions, K in {24, 365} frames (hourly suns
+of one day; one daylight sun per day of a year), each frame with its own turbidity and weight.
+  baseline -- K x (set sun_direction and turbidity, parameters_changed_async, eval,
+              out.add_(tmp, alpha=w)) on one stream
+  sequence -- one SunskySequence.eval
+time.perf_counter around stream-synchronised bursts, warm, median of 5.  Prints one JSON line
+per K: both times, their ratio, and the sequence kernel's frame-evals/s (n K / t: a frame-eval
+does an eval's transcendental work with no HBM traffic).  Not part of bench.py."""
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "mitsuba3-sunsky_amd"))
+import sunsky_amd as ss  # noqa: E402
+
+N = 1 << 21
+REPS = 5
+
+
+def frames(k):
+    if k == 24:
+        times = [(2010, 7, 10, float(h)) for h in range(24)]
+    else:
+        times = [(2010, 1 + (d * 12) // k, 1 + d % 28, 8.0 + (d % 9)) for d in range(k)]
+    dirs = np.stack([ss.sun_coordinates(*t) for t in times]).astype(np.float32)
+    turb = (1.0 + 9.0 * ((7 * np.arange(k)) % k) / max(k - 1, 1)).astype(np.float32)
+    wts = (0.25 + ((5 * np.arange(k)) % 11) / 8.0).astype(np.float32)
+    return dirs, turb, wts
+
+
+def median_ms(step, reps=REPS):
+    step()                      # warm
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        step()
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(ts), ts
+
+
+def main():
+    ks = [int(a) for a in sys.argv[1:]] or [24, 365]
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    g = torch.Generator(device=dev).manual_seed(3)
+    v = torch.randn((3, N), device=dev, generator=g)
+    v[2] = v[2].abs()
+    wi = -(v / v.norm(dim=0, keepdim=True)).contiguous()
+    si = ss.SurfaceInteraction3f(wi=wi)
+    base = {"type": "sunsky", "sun_direction": [0.3, 0.4, 0.866], "turbidity": 3.0, "albedo": 0.2}
+    for k in ks:
+        dirs, turb, wts = frames(k)
+        em = ss.load_dict(dict(base))
+        params = em.traverse()
+        out_loop = torch.empty((3, N), device=dev)
+
+        def baseline():
+            out_loop.zero_()
+            for i in range(k):
+                params["sun_direction"] = dirs[i]
+                params["turbidity"] = float(turb[i])
+                params.update()
+                out_loop.add_(em.eval(si), alpha=float(wts[i]))
+
+        seq = ss.SunskySequence(ss.load_dict(dict(base)), dirs, turb, wts)
+        out_seq = torch.empty((3, N), device=dev)
+        t_seq, all_seq = median_ms(lambda: seq.eval(wi, out=out_seq))
+        t_base, all_base = median_ms(baseline)
+        # Agreement of the two paths.  set_param stages a sun direction as given while a sequence
+        # normalises it like the constructor: an ulp on the sun vector moves the fp32 disc test
+        # dot >= cos_cutoff by ~0.5 % of the disc's solid angle (1 - cos_cutoff = 1.1e-5), so a few
+        # disc-edge lanes per run sit on different sides; every other lane agrees to rounding.
+        rel = (out_seq - out_loop).abs() / out_loop.abs().clamp_min(1e-6 * out_loop.abs().max().item())
+        lanes_off = int((rel > 1e-4).any(dim=0).sum().item())
+        rel_q = float(rel.flatten()[:: 7].quantile(0.999).item())
+        print(json.dumps({"K": k, "n": N, "baseline_ms": round(t_base, 3), "sequence_ms": round(t_seq, 3),
+                          "speedup": round(t_base / t_seq, 2),
+                          "frame_evals_per_s": round(N * k / (t_seq * 1e-3), 0),
+                          "baseline_evals_per_s": round(N * k / (t_base * 1e-3), 0),
+                          "lanes_over_1e-4_vs_loop": lanes_off, "rel_diff_q999": rel_q,
+                          "sequence_ms_all": [round(t, 3) for t in all_seq],
+                          "baseline_ms_all": [round(t, 3) for t in all_base]}), flush=True)
+    print("sequence_bench done")
+
+
+if __name__ == "__main__":
+    main()
