@@ -18,7 +18,8 @@
  *     asynchronous and stream-ordered.  The hot-path calls (eval,
  *     eval_direction, eval_spectral_broadcast, sample_direction, pdf_direction,
  *     sample_ray, sample_wavelengths, direct_diffuse, direct_diffuse_rays,
- *     eval_jvp_dir, eval_vjp_dir, sequence_eval)
+ *     eval_jvp_dir, eval_vjp_dir, sequence_eval, sequence_sample_direction,
+ *     sequence_pdf_direction)
  *     allocate nothing, make no host-synchronous call and may be captured into
  *     a hipGraph (tests/test_graph_capture.py).  Kernels read the emitter state
  *     from device memory, which parameters_changed_async rewrites in place on
@@ -51,7 +52,8 @@ extern "C" {
                                      7: SUNSKY_TABLE_SUN_SEGMENTS, emitter_sun_segments (testing);
                                         added since, additive only (the version stays 7):
                                         eval_jvp_dir, eval_vjp_dir; sun_coordinates and the
-                                        sunsky_sequence_* calls (frame sequences) */
+                                        sunsky_sequence_* calls (frame sequences, their
+                                        sampling included) */
 
 typedef enum sunsky_status {
     SUNSKY_OK = 0,
@@ -271,8 +273,8 @@ int sunsky_bake_latlong(const sunsky_emitter *e, int width, int height, float th
  * A time-lapse, a cumulative-sky map or a time-averaged sky is one launch instead of one
  * restaging and one pass over the rays per instant.
  * Out of scope: per-ray wavelengths (their channel index is per lane, so a frame's record
- * would no longer be wave-uniform), per-ray frame indices, sampling, AD, per-frame albedo /
- * scales / aperture. */
+ * would no longer be wave-uniform), per-ray frame indices, AD, per-frame albedo / scales /
+ * aperture. */
 typedef struct sunsky_sequence sunsky_sequence;
 typedef struct sunsky_sequence_desc {
     int count;        /* frames                       */
@@ -318,6 +320,69 @@ int sunsky_sequence_eval(const sunsky_sequence *seq, sunsky_vec3_in wi, const fl
 int sunsky_sequence_bake_latlong(const sunsky_sequence *seq, int width, int height, float theta0,
                                  float theta1, float phi0, float phi1, const float *wavelengths_host,
                                  int n_wavelengths, float *out, size_t out_stride, void *stream);
+
+/* Importance sampling of a sequence.  The distribution lives in the emitter's local frame
+ * (to_world is applied on the way out, as in sunsky_sample_direction) and has two parts:
+ *  - one table of the cumulative sky over n_z x n_phi cells of equal solid angle
+ *    omega = 2 pi / (n_z n_phi): row i covers z = cos theta in [i / n_z, (i + 1) / n_z) (row 0
+ *    at the horizon, z = 1 in the last row), column j covers phi = atan2(y, x) wrapped to
+ *    [0, 2 pi) in [j dphi, (j + 1) dphi), dphi = 2 pi / n_phi.  The cell value is
+ *    f_ij = Y(sum_k w_k sky_k(centre)) >= 0, the sky term only, Y the luminance
+ *    (0.212671 R + 0.715160 G + 0.072169 B; spectral: sum_c cie_y[c] L_c / 11 over the 11
+ *    nodes), always in reference precision.  S = sum f_ij, sky mass M = S omega.
+ *  - one cone per frame: B_k = Y of frame k's disc term alone at the disc centre (0 for a
+ *    sun below the horizon), sun mass P = Omega_c sum_k w_k B_k with
+ *    Omega_c = 2 pi (1 - cos_cutoff), q_k = w_k B_k / sum_k w_k B_k (all 0 when the sum is 0).
+ * With w_sky = M / (M + P), for a local direction d with z >= 0
+ *     pdf(d) = w_sky f_cell(d) / (S omega)
+ *            + (1 - w_sky) sun_pdf sum_k q_k [dot(s_k, d) >= cos_cutoff]
+ * (the sum in frame order in fp32; 0 for z < 0 and for inactive lanes).  A sample u = (u1, u2)
+ * with u1 < w_sky picks the row from the marginal over the row sums with u2 and the column
+ * from that row's distribution with u1 / w_sky, each with sample reuse:
+ * z = min((i + t2) / n_z, 1), phi = (j + t1) dphi.  Otherwise frame k comes from the q
+ * distribution with (u1 - w_sky) / (1 - w_sky) and d = Frame(s_k).to_world(
+ * square_to_uniform_cone(t1, u2)), its z clamped to 1 like the sky pick's.  A sample is active
+ * when its local z >= 0 (sunsky.cpp:413).  ds.pdf is the pdf above at ds.d taken back to the local frame, so it
+ * equals sunsky_sequence_pdf_direction(ds.d) bit for bit, and the weight is
+ * sum_k w_k eval_k(-ds.d) / ds.pdf (0 where the lane is inactive or the quotient not finite).
+ *
+ * sunsky_sequence_prepare_sampling builds the tables (two launches and a read-back):
+ * host-synchronous like sunsky_sequence_create, not capturable, not to be called while
+ * launches on the sequence are in flight; a second call replaces the tables.
+ * 1 <= n_z <= 1024, 4 <= n_phi <= 4096, n_z n_phi <= 2^20.  M + P == 0 (every frame dark or
+ * of zero weight) is SUNSKY_ERROR_INVALID_VALUE.  Works on host-only sequences too (the
+ * tables then come from the host's libm and agree with the device's to ~1e-5). */
+typedef struct sunsky_sequence_sampling_desc {
+    int n_z, n_phi;
+    float w_sky;       /* M / (M + P)                */
+    float sky_mass;    /* M = S omega                */
+    float sun_mass;    /* P = Omega_c sum_k w_k B_k  */
+} sunsky_sequence_sampling_desc;
+typedef enum sunsky_sequence_table_id {
+    SUNSKY_SEQUENCE_TABLE_SKY = 0,        /* f: n_z x n_phi                                    */
+    SUNSKY_SEQUENCE_TABLE_ROW_CDF = 1,    /* n_z: inclusive, normalised (last entry 1)         */
+    SUNSKY_SEQUENCE_TABLE_CELL_CDF = 2,   /* n_z x n_phi: per row, inclusive, normalised       */
+    SUNSKY_SEQUENCE_TABLE_Q = 3,          /* count                                             */
+    SUNSKY_SEQUENCE_TABLE_FRAME_CDF = 4,  /* count: inclusive, normalised                      */
+    SUNSKY_SEQUENCE_TABLE_B = 5           /* count                                             */
+} sunsky_sequence_table_id;
+int sunsky_sequence_prepare_sampling(sunsky_sequence *seq, int n_z, int n_phi);
+int sunsky_sequence_sampling_info(const sunsky_sequence *seq, sunsky_sequence_sampling_desc *out);
+/* Writes min(count, capacity) floats (out may be NULL to query count). */
+int sunsky_sequence_get_sampling_table(const sunsky_sequence *seq, int id, float *out, size_t capacity,
+                                       size_t *count);
+/* sunsky_sample_direction's layout: sample planes, optional it_p, optional mask; ds_d, ds_pdf
+ * and n_planes weight planes (3 RGB; spectral: one host wavelength list of <= 32 entries as
+ * sunsky_sequence_eval takes it); ds_dist / ds_p optional, formed from the snapshot's bounding
+ * sphere as the emitter forms them.  Both calls are hot-path calls (stream-ordered, no
+ * allocation, capturable); before prepare_sampling they fail with SUNSKY_ERROR_INVALID_VALUE. */
+int sunsky_sequence_sample_direction(const sunsky_sequence *seq, const float *sample_x, const float *sample_y,
+                                     sunsky_vec3_in it_p, const float *wavelengths_host, int n_wavelengths,
+                                     const uint8_t *active, size_t n, sunsky_vec3_out ds_d, float *ds_pdf,
+                                     float *ds_dist, sunsky_vec3_out ds_p, float *weight, size_t weight_stride,
+                                     void *stream);
+int sunsky_sequence_pdf_direction(const sunsky_sequence *seq, sunsky_vec3_in ds_d, const uint8_t *active,
+                                  size_t n, float *pdf, void *stream);
 
 /* A caller of sample_direction / pdf_direction / eval: the sun-and-sky light a
  * smooth-diffuse point receives, gathered as the path integrator does at one vertex

@@ -422,6 +422,34 @@ public:
                                            wavelengths.empty() ? nullptr : wavelengths.data(), (int)wavelengths.size(),
                                            out.data, out.stride ? out.stride : n, stream));
     }
+    // Importance sampling (sunsky_amd.h): build the distribution once, then sample / query it
+    void prepare_sampling(int n_z = 64, int n_phi = 256) { check(sunsky_sequence_prepare_sampling(s_, n_z, n_phi)); }
+    sunsky_sequence_sampling_desc sampling_info() const {
+        sunsky_sequence_sampling_desc d;
+        check(sunsky_sequence_sampling_info(s_, &d));
+        return d;
+    }
+    std::vector<float> sampling_table(sunsky_sequence_table_id id) const {
+        size_t count = 0;
+        check(sunsky_sequence_get_sampling_table(s_, (int)id, nullptr, 0, &count));
+        std::vector<float> t(count);
+        check(sunsky_sequence_get_sampling_table(s_, (int)id, t.data(), count, &count));
+        return t;
+    }
+    // (ds, weight) over n samples; it_p all-null = the origin; weight planes as eval's
+    void sample_direction(size_t n, Point2 sample, DirectionSample ds, SpectrumOut weight, Vector3 it_p = {},
+                          const std::vector<float>& wavelengths = {}, const uint8_t* active = nullptr,
+                          void* stream = nullptr) const {
+        check(sunsky_sequence_sample_direction(s_, sample.x, sample.y, sunsky_vec3_in{it_p.x, it_p.y, it_p.z},
+                                               wavelengths.empty() ? nullptr : wavelengths.data(), (int)wavelengths.size(),
+                                               active, n, sunsky_vec3_out{ds.d.x, ds.d.y, ds.d.z}, ds.pdf, ds.dist,
+                                               sunsky_vec3_out{ds.p.x, ds.p.y, ds.p.z}, weight.data,
+                                               weight.stride ? weight.stride : n, stream));
+    }
+    void pdf_direction(size_t n, const DirectionSampleIn& ds, float* pdf, const uint8_t* active = nullptr,
+                       void* stream = nullptr) const {
+        check(sunsky_sequence_pdf_direction(s_, sunsky_vec3_in{ds.d.x, ds.d.y, ds.d.z}, active, n, pdf, stream));
+    }
     sunsky_sequence_desc info() const {
         sunsky_sequence_desc d;
         check(sunsky_sequence_info(s_, &d));

@@ -161,6 +161,9 @@ void check_xform_form(hipModule_t mod, const std::string& path, bool want_identi
     X(SEQUENCE_EVAL_SPEC, "sunsky_sequence_eval_spec", 64, false, 1)                               \
     X(SEQUENCE_BAKE_RGB, "sunsky_sequence_bake_rgb", 64, false, 1)                                 \
     X(SEQUENCE_BAKE_SPEC, "sunsky_sequence_bake_spec", 64, false, 1)                               \
+    X(SEQUENCE_SAMPLE_RGB, "sunsky_sequence_sample_rgb", 64, false, 1)                             \
+    X(SEQUENCE_SAMPLE_SPEC, "sunsky_sequence_sample_spec", 64, false, 1)                           \
+    X(SEQUENCE_PDF, "sunsky_sequence_pdf", 64, false, 1)                                           \
     X(DEBUG_SUN_SEGMENTS, "sunsky_debug_sun_segments", 16, false, 1)
 
 #define X(id, name, wg, dir, per) K_##id,
@@ -190,6 +193,7 @@ struct DeviceModule {
     hipFunction_t stage_radiance = nullptr, quad_points = nullptr, quad_finish = nullptr;   // parameters_changed
     hipFunction_t stage_tangent = nullptr;                                      // eval_jvp / eval_vjp tables
     hipFunction_t stage_sequence = nullptr;                                     // sequence_create
+    hipFunction_t sequence_table = nullptr, sequence_suns = nullptr;            // sequence_prepare_sampling
     int cu_count = 256;
 };
 
@@ -231,6 +235,8 @@ DeviceModule* module_for_device(int dev) {
     get(&m->latlong_tables, m->module, "sunsky_latlong_tables");
     get(&m->stage_tangent, m->module, "sunsky_stage_tangent");
     get(&m->stage_sequence, m->module, "sunsky_stage_sequence");
+    get(&m->sequence_table, m->module, "sunsky_sequence_table");
+    get(&m->sequence_suns, m->module, "sunsky_sequence_suns");
     get(&m->stage_radiance, m->module, "sunsky_stage_radiance");
     get(&m->quad_points, m->module, "sunsky_stage_quad_points");
     get(&m->quad_finish, m->module, "sunsky_stage_quad_finish");
@@ -649,9 +655,23 @@ struct sunsky_sequence {
     mutable float* d_bake = nullptr;         // bake_latlong angle tables, ordered as the emitter's
     mutable size_t bake_cap = 0;
     mutable hipEvent_t bake_done = nullptr;
+    // sampling (prepare_sampling): the snapshot's luminance weights and, for host-only
+    // sequences, the tables the disc term reads; then the distribution itself
+    float cie_y[kNbWavelengths] = {0};
+    std::vector<float> h_sun_rad, h_sun_ld;
+    int samp_nz = 0, samp_nphi = 0;          // 0: not prepared
+    float samp_w_sky = 0.f, samp_sky_mass = 0.f, samp_sun_mass = 0.f;
+    std::vector<float> samp_f, samp_row_cdf, samp_cell_cdf, samp_q, samp_frame_cdf, samp_B;
+    float* d_samp = nullptr;                 // f, row_cdf, cell_cdf, frame_cdf, suns in one block
+    SeqSampling samp = {};
 
     void require_device() const {
         if (!mod) throw std::invalid_argument("host-only sequence (over a sunsky_emitter_create_host emitter) cannot launch kernels");
+    }
+    void require_sampling() const {
+        if (!samp_nz)
+            throw std::invalid_argument("the sequence has no sampling distribution yet: call "
+                                        "sunsky_sequence_prepare_sampling first");
     }
     // The snapshot never changes, so an identity to_world takes the identity code object under
     // capture too (SUNSKY_AMD_GENERAL_XFORM=1: the general one always)
@@ -666,7 +686,7 @@ struct sunsky_sequence {
         int cur = -1;
         if (hipGetDevice(&cur) == hipSuccess && cur != device) (void)hipSetDevice(device);
         (void)hipDeviceSynchronize();   // launches in flight may still read the records
-        for (void* p : {(void*)d_state, d_frames, (void*)d_sun_rad, (void*)d_sun_ld, (void*)d_bake})
+        for (void* p : {(void*)d_state, d_frames, (void*)d_sun_rad, (void*)d_sun_ld, (void*)d_bake, (void*)d_samp})
             if (p) (void)hipFree(p);
         if (bake_done) (void)hipEventDestroy(bake_done);
         if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
@@ -736,6 +756,155 @@ void seq_stage_host(sunsky_sequence* q, const SunskyModel& model, float sky_scal
         SkyChannel* sky = reinterpret_cast<SkyChannel*>(rec + kSeqFrameHeader + (size_t)nch * sizeof(FastChannel));
         for (int c = 0; c < nch; ++c) fold_channel(&p[c * kNbSkyParams], r[c], q->variant, sky_scale, &sky[c], &fast[c]);
     }
+}
+
+// ---- sampling tables (sunsky_sequence_prepare_sampling)
+// sunsky_sequence_table / sunsky_sequence_suns on the host (host-only sequences): the same
+// definitions through the SS_HD functions, with the host's libm
+void seq_sampling_host(const sunsky_sequence* q, int nz, int nphi, std::vector<float>& f, std::vector<float>& B) {
+    const SunskyKArgs& K = q->kargs;
+    const bool rgb = q->variant == kRGB;
+    const float cie = (float)kCieYNormalization;
+    for (int i = 0; i < nz; ++i)
+        for (int j = 0; j < nphi; ++j) {
+            const float3_ wo = seq_cell_centre(nz, nphi, i, j);
+            float acc[kNbWavelengths] = {0};
+            for (int k = 0; k < q->count; ++k) {
+                const SeqFrame<1>* h = seq_header(q, k);
+                const SkyChannel* sky = seq_sky(q, k);
+                const float gamma = unit_angle(mk3(h->sun_n[0], h->sun_n[1], h->sun_n[2]), wo);
+                for (int c = 0; c < q->nch; ++c) {
+                    const float v = K.sky_scale * render_sky(sky[c], wo.z, gamma);
+                    acc[c] = fmaf(h->weight, rgb ? v * cie : v, acc[c]);
+                }
+            }
+            float y = 0.f;
+            if (rgb) y = luminance_rgb(acc);
+            else {
+                for (int c = 0; c < kNbWavelengths; ++c) y = fmaf(q->cie_y[c], acc[c], y);
+                y = y / (float)kNbWavelengths;
+            }
+            f[(size_t)i * nphi + j] = std::fmax(y, 0.f);
+        }
+    const float* ds = q->h_sun_rad.data();
+    for (int k = 0; k < q->count; ++k) {
+        const SeqFrame<1>* h = seq_header(q, k);
+        const float3_ sn = mk3(h->sun_n[0], h->sun_n[1], h->sun_n[2]);
+        B[k] = 0.f;
+        if (!(sn.z >= 0.f) || !(dot3(sn, sn) >= K.cos_cutoff)) continue;
+        const RadianceStage rs = {0.f, h->t_rem, h->t_low, h->t_high, 1};
+        int pos = 0;
+        for (int j = 1; j < kNbSunSegments; ++j) pos += sn.z >= K.sun_seg_z[j] ? 1 : 0;
+        const float frac = (float)pos / (float)kNbSunSegments;
+        const float xs = (kHalfPi - acosf(sn.z)) - kHalfPi * (frac * frac * frac);
+        const float cpsi = cos_psi(unit_angle(sn, sn), K.inv_sin2_half_ap);
+        float y = 0.f;
+        if (rgb) {
+            constexpr int per_c = kNbSunCtrlPts * kNbSunLdParams;
+            float v[3];
+            for (int c = 0; c < 3; ++c) {
+                float s[per_c];
+                for (int e = 0; e < per_c; ++e) s[e] = sun_param(ds, q->sun_block, pos * (3 * per_c) + c * per_c + e, rs);
+                v[c] = K.sun_scale * render_sun_rgb(s, 0, 0, xs, cpsi) * K.area_ratio * (float)kSpecToRgbSunConv;
+            }
+            y = luminance_rgb(v) * cie;
+        } else {
+            for (int c = 0; c < kNbWavelengths; ++c) {
+                float sun = 0.f;
+                for (int e = 0; e < kNbSunCtrlPts; ++e)
+                    sun += powif_(xs, e) * sun_param(ds, q->sun_block, (pos * kNbWavelengths + c) * kNbSunCtrlPts + e, rs);
+                const float ld = sun_limb_darkening(q->h_sun_ld.data(), c, c + 1, 0.f, cpsi);
+                y = fmaf(q->cie_y[c], K.sun_scale * sun * ld * K.area_ratio, y);
+            }
+            y = y / (float)kNbWavelengths;
+        }
+        B[k] = std::fmax(y, 0.f);
+    }
+}
+
+// Inclusive normalised CDF of n non-negative values: last entry 1, and 1 from the last
+// non-zero value on, so a sample below 1 never lands on a trailing zero (all zero: uniform)
+void seq_cdf(const double* v, int n, float* out) {
+    double total = 0.0;
+    int last = -1;
+    for (int j = 0; j < n; ++j) {
+        total += v[j];
+        if (v[j] > 0.0) last = j;
+    }
+    double cum = 0.0;
+    for (int j = 0; j < n; ++j) {
+        cum += v[j];
+        out[j] = last < 0 ? (float)((double)(j + 1) / (double)n) : (j >= last ? 1.f : (float)(cum / total));
+    }
+    out[n - 1] = 1.f;
+}
+
+// Floats of the device block: f, row_cdf, cell_cdf, frame_cdf, suns, each 16-byte aligned
+struct SeqSamplingLayout {
+    size_t f, row_cdf, cell_cdf, frame_cdf, suns, total;
+    SeqSamplingLayout(int nz, int nphi, int count) {
+        auto up = [](size_t x) { return (x + 3) & ~(size_t)3; };
+        const size_t cells = (size_t)nz * (size_t)nphi;
+        f = 0;
+        row_cdf = up(cells);
+        cell_cdf = row_cdf + up((size_t)nz);
+        frame_cdf = cell_cdf + up(cells);
+        suns = frame_cdf + up((size_t)count);
+        total = suns + 4 * (size_t)count;
+    }
+};
+
+// From the table and B_k to the distribution: masses, w_sky, q, the CDFs
+void seq_sampling_finish(sunsky_sequence* q, int nz, int nphi, std::vector<float>&& f, std::vector<float>&& B) {
+    const int K = q->count;
+    const size_t cells = (size_t)nz * (size_t)nphi;
+    std::vector<double> rows(nz), tmp(std::max(nphi, K));
+    std::vector<float> row_cdf(nz), cell_cdf(cells), qv(K), frame_cdf(K);
+    double S = 0.0;
+    for (int i = 0; i < nz; ++i) {
+        double r = 0.0;
+        for (int j = 0; j < nphi; ++j) {
+            tmp[j] = f[(size_t)i * nphi + j];
+            r += tmp[j];
+        }
+        rows[i] = r;
+        S += r;
+        seq_cdf(tmp.data(), nphi, &cell_cdf[(size_t)i * nphi]);
+    }
+    seq_cdf(rows.data(), nz, row_cdf.data());
+    const double omega = 2.0 * 3.14159265358979323846 / (double)cells;
+    const double M = S * omega;
+    double wb = 0.0;
+    for (int k = 0; k < K; ++k) {
+        tmp[k] = (double)seq_header(q, k)->weight * (double)B[k];
+        wb += tmp[k];
+    }
+    const double P = 2.0 * 3.14159265358979323846 * (1.0 - (double)q->kargs.cos_cutoff) * wb;
+    if (!std::isfinite(M + P) || !(M + P > 0.0))
+        throw std::invalid_argument("the sequence is dark (every frame has zero weight or no radiance above the "
+                                    "horizon): sky mass + sun mass == 0, there is nothing to sample");
+    for (int k = 0; k < K; ++k) qv[k] = wb > 0.0 ? (float)(tmp[k] / wb) : 0.f;
+    seq_cdf(tmp.data(), K, frame_cdf.data());
+    const float w_sky = (float)(M / (M + P));
+    q->samp_w_sky = w_sky;
+    q->samp_sky_mass = (float)M;
+    q->samp_sun_mass = (float)P;
+    q->samp_f = std::move(f);
+    q->samp_B = std::move(B);
+    q->samp_row_cdf = std::move(row_cdf);
+    q->samp_cell_cdf = std::move(cell_cdf);
+    q->samp_q = std::move(qv);
+    q->samp_frame_cdf = std::move(frame_cdf);
+    for (int k = 0; k < K; ++k) seq_header(q, k)->pad[0] = q->samp_q[k];
+    SeqSampling& s = q->samp;
+    std::memset(&s, 0, sizeof(s));
+    s.nz = nz;
+    s.nphi = nphi;
+    s.w_sky = w_sky;
+    s.sky_coef = M > 0.0 ? (float)((double)w_sky / M) : 0.f;
+    s.sun_coef = (1.f - w_sky) * q->kargs.sun_pdf;
+    s.dphi = kTwoPi / (float)nphi;
+    s.inv_dphi = (float)nphi / kTwoPi;
 }
 
 }  // namespace
@@ -1484,7 +1653,10 @@ int sunsky_sequence_create(const sunsky_emitter* e, int count, const float* sun_
         q->rec_bytes = kSeqFrameHeader + (size_t)q->nch * (sizeof(FastChannel) + sizeof(SkyChannel));
         q->records.assign((size_t)count * q->rec_bytes, 0);
         seq_fill_headers(q.get(), model, sun_dirs, turbidity, weights);
+        std::memcpy(q->cie_y, model.cie_y(), sizeof(q->cie_y));
         if (e->device < 0) {
+            q->h_sun_rad = model.sun_rad_ds();   // prepare_sampling's disc term on the host
+            q->h_sun_ld = model.sun_ld();
             seq_stage_host(q.get(), model, q->kargs.sky_scale);
             *out = q.release();
             return;
@@ -1641,6 +1813,161 @@ int sunsky_sequence_bake_latlong(const sunsky_sequence* seq, int width, int heig
             run_kernel(seq->mod, seq->xform_form(), seq->precision, K_SEQUENCE_BAKE_SPEC, n, args, s);
         }
         hip_check(hipEventRecord(seq->bake_done, s), "hipEventRecord");
+    });
+}
+
+int sunsky_sequence_prepare_sampling(sunsky_sequence* seq, int n_z, int n_phi) {
+    SUNSKY_PHASE("InitScene", "sequence_prepare_sampling");
+    if (!seq) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sequence");
+    if (n_z < 1 || n_z > kSeqSampleMaxZ || n_phi < 4 || n_phi > kSeqSampleMaxPhi ||
+        (int64_t)n_z * n_phi > kSeqSampleMaxCells)
+        return fail(SUNSKY_ERROR_INVALID_VALUE,
+                    "sampling table size out of range: 1 <= n_z <= 1024, 4 <= n_phi <= 4096, n_z * n_phi <= 2^20");
+    return guarded([&] {
+        const size_t cells = (size_t)n_z * (size_t)n_phi;
+        std::vector<float> f(cells), B(seq->count);
+        if (seq->device < 0) {
+            seq_sampling_host(seq, n_z, n_phi, f, B);
+            seq_sampling_finish(seq, n_z, n_phi, std::move(f), std::move(B));
+            seq->samp_nz = n_z;
+            seq->samp_nphi = n_phi;
+            return;
+        }
+        DeviceScope g(seq->device);
+        const SeqSamplingLayout lay(n_z, n_phi, seq->count);
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");   // nothing may still read the old tables
+        seq->samp_nz = seq->samp_nphi = 0;
+        if (seq->d_samp) hip_check(hipFree(seq->d_samp), "hipFree");
+        seq->d_samp = nullptr;
+        hip_check(hipMalloc(&seq->d_samp, sizeof(float) * lay.total), "hipMalloc");
+        hip_check(hipMemset(seq->d_samp, 0, sizeof(float) * lay.total), "hipMemset");
+        SeqTableArgs T;
+        std::memset(&T, 0, sizeof(T));
+        T.f = seq->d_samp + lay.f;
+        T.B = seq->d_samp + lay.suns;   // B_k rests where the sun records go
+        std::memcpy(T.cie_y, seq->cie_y, sizeof(T.cie_y));
+        T.nz = n_z;
+        T.nphi = n_phi;
+        const SunskyKArgs* K = seq->d_state;
+        SeqArgs A = seq->args();
+        void* args[] = {&K, &A, &T};
+        const unsigned grid = (unsigned)std::min<size_t>((cells + kBlock - 1) / kBlock, (size_t)seq->mod->cu_count * 64);
+        launch(seq->mod->sequence_table, grid, nullptr, args);
+        hip_check(hipModuleLaunchKernel(seq->mod->sequence_suns, (unsigned)std::min(seq->count, 65535), 1, 1, 64, 1, 1, 0,
+                                        nullptr, args, nullptr), "hipModuleLaunchKernel(sunsky_sequence_suns)");
+        hip_check(hipStreamSynchronize(nullptr), "hipStreamSynchronize");
+        hip_check(hipMemcpy(f.data(), T.f, sizeof(float) * cells, hipMemcpyDeviceToHost), "hipMemcpy");
+        hip_check(hipMemcpy(B.data(), T.B, sizeof(float) * seq->count, hipMemcpyDeviceToHost), "hipMemcpy");
+        seq_sampling_finish(seq, n_z, n_phi, std::move(f), std::move(B));
+        std::vector<float> block(lay.total, 0.f);
+        std::copy(seq->samp_f.begin(), seq->samp_f.end(), block.begin() + lay.f);
+        std::copy(seq->samp_row_cdf.begin(), seq->samp_row_cdf.end(), block.begin() + lay.row_cdf);
+        std::copy(seq->samp_cell_cdf.begin(), seq->samp_cell_cdf.end(), block.begin() + lay.cell_cdf);
+        std::copy(seq->samp_frame_cdf.begin(), seq->samp_frame_cdf.end(), block.begin() + lay.frame_cdf);
+        for (int k = 0; k < seq->count; ++k) {
+            const SeqFrame<1>* h = seq_header(seq, k);
+            float* r = &block[lay.suns + 4 * (size_t)k];
+            r[0] = h->sun_n[0]; r[1] = h->sun_n[1]; r[2] = h->sun_n[2];
+            r[3] = seq->samp_q[k];
+        }
+        hip_check(hipMemcpy(seq->d_samp, block.data(), sizeof(float) * lay.total, hipMemcpyHostToDevice), "hipMemcpy");
+        // q_k into the records (SeqFrame::pad[0]): the sample kernels read it beside the header
+        hip_check(hipMemcpy(seq->d_frames, seq->records.data(), seq->records.size(), hipMemcpyHostToDevice), "hipMemcpy");
+        SeqSampling& s = seq->samp;
+        s.f = seq->d_samp + lay.f;
+        s.row_cdf = seq->d_samp + lay.row_cdf;
+        s.cell_cdf = seq->d_samp + lay.cell_cdf;
+        s.frame_cdf = seq->d_samp + lay.frame_cdf;
+        s.suns = seq->d_samp + lay.suns;
+        seq->samp_nz = n_z;
+        seq->samp_nphi = n_phi;
+    });
+}
+
+int sunsky_sequence_sampling_info(const sunsky_sequence* seq, sunsky_sequence_sampling_desc* out) {
+    if (!seq || !out) return fail(SUNSKY_ERROR_INVALID_VALUE, "null argument");
+    return guarded([&] {
+        seq->require_sampling();
+        out->n_z = seq->samp_nz;
+        out->n_phi = seq->samp_nphi;
+        out->w_sky = seq->samp_w_sky;
+        out->sky_mass = seq->samp_sky_mass;
+        out->sun_mass = seq->samp_sun_mass;
+    });
+}
+
+int sunsky_sequence_get_sampling_table(const sunsky_sequence* seq, int id, float* out, size_t cap, size_t* count) {
+    if (!seq) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sequence");
+    return guarded([&] {
+        seq->require_sampling();
+        const std::vector<float>* t = nullptr;
+        switch (id) {
+            case SUNSKY_SEQUENCE_TABLE_SKY: t = &seq->samp_f; break;
+            case SUNSKY_SEQUENCE_TABLE_ROW_CDF: t = &seq->samp_row_cdf; break;
+            case SUNSKY_SEQUENCE_TABLE_CELL_CDF: t = &seq->samp_cell_cdf; break;
+            case SUNSKY_SEQUENCE_TABLE_Q: t = &seq->samp_q; break;
+            case SUNSKY_SEQUENCE_TABLE_FRAME_CDF: t = &seq->samp_frame_cdf; break;
+            case SUNSKY_SEQUENCE_TABLE_B: t = &seq->samp_B; break;
+            default: throw std::invalid_argument("unknown sequence sampling table id");
+        }
+        if (count) *count = t->size();
+        if (out) std::memcpy(out, t->data(), sizeof(float) * std::min(cap, t->size()));
+    });
+}
+
+int sunsky_sequence_sample_direction(const sunsky_sequence* seq, const float* ux, const float* uy, sunsky_vec3_in it_p,
+                                     const float* lam_host, int m, const uint8_t* active, size_t n,
+                                     sunsky_vec3_out ds_d, float* ds_pdf, float* ds_dist, sunsky_vec3_out ds_p,
+                                     float* weight, size_t wstride, void* stream) {
+    SUNSKY_PHASE("EndpointSampleDirection", "sequence_sample_direction");
+    if (!seq) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sequence");
+    const bool spec = seq->variant == kSpectral;
+    if (spec && (!lam_host || m < 1 || m > kMaxBroadcastLambda))
+        return fail(SUNSKY_ERROR_INVALID_VALUE, "1..32 broadcast wavelengths required for a spectral sequence");
+    if (!spec && lam_host && m) return fail(SUNSKY_ERROR_INVALID_VALUE, "an RGB sequence takes no wavelengths");
+    if (n == 0) return SUNSKY_OK;
+    if (!ux || !uy || !ds_d.x || !ds_d.y || !ds_d.z || !ds_pdf || !weight)
+        return fail(SUNSKY_ERROR_INVALID_VALUE, "null sample / output pointer");
+    if ((spec ? m : 3) > 1 && wstride < n) return fail(SUNSKY_ERROR_INVALID_VALUE, "weight_stride < n");
+    if ((it_p.x != nullptr) != (it_p.y != nullptr) || (it_p.x != nullptr) != (it_p.z != nullptr))
+        return fail(SUNSKY_ERROR_INVALID_VALUE, "it_p must be all-NULL or all-set");
+    if ((ds_p.x != nullptr) != (ds_p.y != nullptr) || (ds_p.x != nullptr) != (ds_p.z != nullptr))
+        return fail(SUNSKY_ERROR_INVALID_VALUE, "ds_p must be all-NULL or all-set");
+    return guarded([&] {
+        seq->require_sampling();   // first: the message names the missing call on any sequence
+        seq->require_device();
+        DeviceScope g(seq->device);
+        const SunskyKArgs* K = seq->d_state;
+        SeqArgs A = seq->args();
+        SeqSampling S = seq->samp;
+        SeqSampleIO io = {ux, uy, it_p.x, it_p.y, it_p.z, active, ds_d.x, ds_d.y, ds_d.z, ds_pdf, ds_dist,
+                          ds_p.x, ds_p.y, ds_p.z, weight, wstride};
+        if (!spec) {
+            void* args[] = {&K, &A, &S, &io, &n};
+            run_kernel(seq->mod, seq->xform_form(), seq->precision, K_SEQUENCE_SAMPLE_RGB, n, args, (hipStream_t)stream);
+        } else {
+            LambdaSet L = make_lambda_set(lam_host, m);
+            void* args[] = {&K, &A, &S, &L, &io, &n};
+            run_kernel(seq->mod, seq->xform_form(), seq->precision, K_SEQUENCE_SAMPLE_SPEC, n, args, (hipStream_t)stream);
+        }
+    });
+}
+
+int sunsky_sequence_pdf_direction(const sunsky_sequence* seq, sunsky_vec3_in d, const uint8_t* active, size_t n,
+                                  float* pdf, void* stream) {
+    SUNSKY_PHASE("EndpointEvaluate", "sequence_pdf_direction");
+    if (!seq) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sequence");
+    if (n == 0) return SUNSKY_OK;
+    if (!d.x || !d.y || !d.z || !pdf) return fail(SUNSKY_ERROR_INVALID_VALUE, "null direction / output pointer");
+    return guarded([&] {
+        seq->require_sampling();   // first: the message names the missing call on any sequence
+        seq->require_device();
+        DeviceScope g(seq->device);
+        const SunskyKArgs* K = seq->d_state;
+        SeqSampling S = seq->samp;
+        int count = seq->count;
+        void* args[] = {&K, &S, &count, (void*)&d.x, (void*)&d.y, (void*)&d.z, &active, &n, &pdf};
+        run_kernel(seq->mod, seq->xform_form(), seq->precision, K_SEQUENCE_PDF, n, args, (hipStream_t)stream);
     });
 }
 

@@ -111,4 +111,48 @@ struct SeqArgs {
 };
 static_assert(sizeof(SeqArgs) == 24, "SeqArgs layout");
 
+// ---------------------------------------------------------------- sequence sampling
+// The sampling distribution of a sequence (sunsky_sequence_prepare_sampling), all in the
+// emitter's local frame: one equal-solid-angle table of the cumulative sky's luminance
+// (row i: z = cos theta in [i / nz, (i + 1) / nz), column j: phi in [j dphi, (j + 1) dphi))
+// and one cone per frame.
+//   pdf(d) = sky_coef f[cell(d)] + sun_coef sum_k q_k [dot(s_k, d) >= cos_cutoff]
+// with sky_coef = w_sky / (S omega) and sun_coef = (1 - w_sky) sun_pdf.  Every CDF is
+// normalised and inclusive (last entry 1); entry j is picked by u when cdf[j - 1] <= u < cdf[j].
+constexpr size_t kSeqFrameQ = 10;   // SeqFrame::pad[0] as a float index: q_k, beside the header's scalar load
+constexpr int kSeqSampleMaxZ = 1024, kSeqSampleMaxPhi = 4096, kSeqSampleMaxCells = 1 << 20;
+
+struct SeqSampling {
+    const float* f;            // [nz][nphi] cell values
+    const float* row_cdf;      // [nz] marginal over the row sums
+    const float* cell_cdf;     // [nz][nphi] per-row distribution
+    const float* frame_cdf;    // [count] over q
+    const float* suns;         // [count] x {s_k.xyz, q_k}: the pdf kernel's 16-byte records
+    int nz, nphi;
+    float w_sky, sky_coef, sun_coef;
+    float dphi, inv_dphi;
+    int pad;
+};
+static_assert(sizeof(SeqSampling) == 72 && offsetof(SeqSampling, nz) == 40, "SeqSampling layout");
+
+// The sample kernels' batch: u, it.p (optional) and the mask in; ds.d, ds.pdf, ds.dist /
+// ds.p (optional) and the weight planes out
+struct SeqSampleIO {
+    const float *ux, *uy, *px, *py, *pz;
+    const uint8_t* active;
+    float *dx, *dy, *dz, *pdf, *dist, *opx, *opy, *opz, *weight;
+    size_t wstride;
+};
+static_assert(sizeof(SeqSampleIO) == 128, "SeqSampleIO layout");
+
+// sunsky_sequence_table / sunsky_sequence_suns (prepare_sampling): one lane per cell / frame
+struct SeqTableArgs {
+    float* f;                  // [nz][nphi], written
+    float* B;                  // [count] disc-centre luminance per frame, written
+    float cie_y[kNbWavelengths];
+    int nz, nphi;
+    int pad;
+};
+static_assert(sizeof(SeqTableArgs) == 16 + 4 * kNbWavelengths + 12, "SeqTableArgs layout");
+
 }  // namespace sunsky

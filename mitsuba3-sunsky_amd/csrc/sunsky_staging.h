@@ -205,6 +205,17 @@ SS_HD inline void fold_channel(const float* p, float rad, int variant, float sky
     f->pad[0] = f->pad[1] = 0.f;
 }
 
+// Sequence sampling (sunsky_sequence_prepare_sampling): the centre of cell (i, j) of the
+// equal-solid-angle table, z = (i + 1/2) / nz, phi = (j + 1/2) 2 pi / nphi, in the local frame,
+// and the luminance weights of an RGB triple (quad_finish's).
+SS_HD inline float3_ seq_cell_centre(int nz, int nphi, int i, int j) {
+    const float z = ((float)i + 0.5f) / (float)nz;
+    const float phi = ((float)j + 0.5f) * (kTwoPi / (float)nphi);
+    const float st = safe_sqrtf_(1.f - z * z);
+    return mk3(st * cosf(phi), st * sinf(phi), z);
+}
+SS_HD inline float luminance_rgb(const float* v) { return v[0] * 0.212671f + v[1] * 0.715160f + v[2] * 0.072169f; }
+
 // estimate_sky_sun_ratio (sunsky.cpp:772-886): quadrature point (i, j) of the
 // 200 x 200 Gauss-Legendre grid, sky over the hemisphere and sun over its cone.  The
 // direction terms are shared by every channel; row j's per-channel sums over i, in

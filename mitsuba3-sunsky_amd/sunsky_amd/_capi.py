@@ -57,6 +57,13 @@ class SequenceDesc(C.Structure):
                 ("device", C.c_int)]
 
 
+class SequenceSamplingDesc(C.Structure):
+    _fields_ = [("n_z", C.c_int), ("n_phi", C.c_int), ("w_sky", C.c_float), ("sky_mass", C.c_float),
+                ("sun_mass", C.c_float)]
+
+
+SEQUENCE_TABLES = {"sky": 0, "row_cdf": 1, "cell_cdf": 2, "q": 3, "frame_cdf": 4, "B": 5}
+
 _SIGS = {
     "sunsky_abi_version": (C.c_int, []),
     "sunsky_last_error": (C.c_char_p, []),
@@ -107,6 +114,12 @@ _SIGS = {
     "sunsky_sequence_eval": (C.c_int, [vp, Vec3In, c_float_p, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp]),
     "sunsky_sequence_bake_latlong": (C.c_int, [vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
                                                c_float_p, C.c_int, vp, C.c_size_t, vp]),
+    "sunsky_sequence_prepare_sampling": (C.c_int, [vp, C.c_int, C.c_int]),
+    "sunsky_sequence_sampling_info": (C.c_int, [vp, C.POINTER(SequenceSamplingDesc)]),
+    "sunsky_sequence_get_sampling_table": (C.c_int, [vp, C.c_int, c_float_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "sunsky_sequence_sample_direction": (C.c_int, [vp, vp, vp, Vec3In, c_float_p, C.c_int, vp, C.c_size_t, Vec3Out,
+                                                   vp, vp, Vec3Out, vp, C.c_size_t, vp]),
+    "sunsky_sequence_pdf_direction": (C.c_int, [vp, Vec3In, vp, C.c_size_t, vp, vp]),
     "sunsky_direct_diffuse": (C.c_int, [vp, Vec3In, vp, vp, C.c_int, C.c_size_t, C.c_uint32, C.c_uint32,
                                         vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp]),
     "sunsky_direct_diffuse_rays": (C.c_int, [vp, Vec3In, C.c_uint32, C.c_uint32, C.c_size_t, Vec3Out, Vec3Out,

@@ -149,5 +149,75 @@ class SunskySequence:
                                                  self._stream()))
         return out
 
+    # ------------------------------------------------------------ importance sampling
+    def prepare_sampling(self, n_z=64, n_phi=256):
+        """Builds the sampling distribution (sunsky_sequence_prepare_sampling): an n_z x n_phi
+        equal-solid-angle table of the cumulative sky's luminance and one cone per frame.
+        Host-synchronous; a second call replaces the tables.  Works on host-only sequences."""
+        check(lib().sunsky_sequence_prepare_sampling(self._h, int(n_z), int(n_phi)))
+
+    def sampling_info(self):
+        d = _capi.SequenceSamplingDesc()
+        check(lib().sunsky_sequence_sampling_info(self._h, C.byref(d)))
+        return {"n_z": d.n_z, "n_phi": d.n_phi, "w_sky": d.w_sky, "sky_mass": d.sky_mass, "sun_mass": d.sun_mass}
+
+    def sampling_table(self, name):
+        """One table of the distribution as fp32: "sky" (n_z, n_phi), "row_cdf" (n_z,), "cell_cdf"
+        (n_z, n_phi), "q", "frame_cdf", "B" (count,)."""
+        tid = _capi.SEQUENCE_TABLES[name]
+        cnt = C.c_size_t()
+        check(lib().sunsky_sequence_get_sampling_table(self._h, tid, None, 0, C.byref(cnt)))
+        buf = (C.c_float * cnt.value)()
+        check(lib().sunsky_sequence_get_sampling_table(self._h, tid, buf, cnt.value, C.byref(cnt)))
+        a = np.array(buf, dtype=np.float32)
+        if name in ("sky", "cell_cdf"):
+            i = self.sampling_info()
+            a = a.reshape(i["n_z"], i["n_phi"])
+        return a
+
+    def sample_direction(self, it, sample, wavelengths=None, active=None):
+        """(DirectionSample3f, weight) in SunskyEmitter.sample_direction's shape: ds.d, ds.pdf,
+        ds.p / ds.dist from it.p (None = origin) and the snapshot's bounding sphere, and
+        weight = sum_k w_k eval_k(-ds.d) / ds.pdf as (3, n) RGB or (m, n) for one wavelength list."""
+        from .records import DirectionSample3f
+        if self.device is None:
+            self.sampling_info()   # an unprepared sequence says so first
+            raise ValueError("host-only sequence (over a host-only emitter) cannot launch kernels")
+        sample = self._f32(sample)
+        if sample.dim() != 2 or sample.shape[0] != 2:
+            raise ValueError("sample is a (2, n) tensor")
+        n = sample.shape[1]
+        k, lam_p, m = self._lambda(wavelengths, "sequence sample_direction")
+        mask = SunskyEmitter._mask(self, active, n)
+        p = getattr(it, "p", None) if it is not None else None
+        if p is not None:
+            p, pin = SunskyEmitter._vec_in(self, p, n, "it.p")
+        else:
+            pin = Vec3In(None, None, None)
+        d = torch.empty((3, n), dtype=torch.float32, device=self.device)
+        pos = torch.empty((3, n), dtype=torch.float32, device=self.device)
+        pdf = torch.empty(n, dtype=torch.float32, device=self.device)
+        dist = torch.empty(n, dtype=torch.float32, device=self.device)
+        w = torch.empty((k, n), dtype=torch.float32, device=self.device)
+        check(lib().sunsky_sequence_sample_direction(
+            self._h, _ptr(sample[0]), _ptr(sample[1]), pin, lam_p, m, _ptr(mask), n,
+            _capi.Vec3Out(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr()), _ptr(pdf), _ptr(dist),
+            _capi.Vec3Out(pos[0].data_ptr(), pos[1].data_ptr(), pos[2].data_ptr()), _ptr(w), n, self._stream()))
+        ds = DirectionSample3f(p=pos, n=-d, uv=sample, time=getattr(it, "time", None), pdf=pdf, delta=False, d=d,
+                               dist=dist, emitter=self)
+        return ds, w
+
+    def pdf_direction(self, it, ds, active=None):
+        """The sampling density of ds.d (n,): what sample_direction stores in ds.pdf."""
+        if self.device is None:
+            self.sampling_info()
+            raise ValueError("host-only sequence (over a host-only emitter) cannot launch kernels")
+        d, vin = SunskyEmitter._vec_in(self, getattr(ds, "d", ds))
+        n = d.shape[1]
+        mask = SunskyEmitter._mask(self, active, n)
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        check(lib().sunsky_sequence_pdf_direction(self._h, vin, _ptr(mask), n, _ptr(out), self._stream()))
+        return out
+
     # SunskyEmitter's tensor helpers read only self.device
     _f32 = SunskyEmitter._f32

@@ -1,0 +1,39 @@
+"""SunskySequence's sampling calls through the C++ facade (include/sunsky_amd.hpp), driven by
+a compiled stand-alone program, tests/cpp/sequence_sampling_check.cpp, in host mode: prepare,
+info, the read-backs and the refusal texts as a C++ renderer linking libsunsky_amd.so sees
+them.  The test compiles the program itself (one translation unit against the built library)."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+import sunsky_amd as ss
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
+
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    if shutil.which("g++") is None:
+        pytest.skip("no g++ to build the sequence sampling check")
+    out = str(tmp_path_factory.mktemp("sequence_sampling_check") / "sequence_sampling_check")
+    libdir = os.path.dirname(ss.LIB_PATH)
+    cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-D__HIP_PLATFORM_AMD__",
+           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROCM, "include"), "-o", out,
+           os.path.join(ROOT, "tests", "cpp", "sequence_sampling_check.cpp"),
+           "-L" + libdir, "-lsunsky_amd", "-Wl,-rpath," + libdir,
+           "-L" + os.path.join(ROCM, "lib"), "-lamdhip64", "-Wl,-rpath," + os.path.join(ROCM, "lib")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    return out
+
+
+def test_sequence_sampling_facade_host_mode(exe):
+    r = subprocess.run([exe, "host"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "sequence sampling host ok" in r.stdout
+    assert "FAILED" not in r.stdout
+    assert "sunsky_sequence_prepare_sampling first" in r.stdout
+    assert "the sequence is dark" in r.stdout

@@ -7,7 +7,9 @@ of one day; one daylight sun per day of a year), each frame with its own turbidi
   sequence -- one SunskySequence.eval
 time.perf_counter around stream-synchronised bursts, warm, median of 5.  Prints one JSON line
 per K: both times, their ratio, and the sequence kernel's frame-evals/s (n K / t: a frame-eval
-does an eval's transcendental work with no HBM traffic).  Not part of bench.py."""
+does an eval's transcendental work with no HBM traffic).  Not part of bench.py.
+  --sampling -- instead: sample_direction and pdf_direction of the prepared sequence beside
+                sequence.eval at the sampled directions (see sampling())."""
 import json
 import os
 import statistics
@@ -47,10 +49,45 @@ def median_ms(step, reps=REPS):
     return statistics.median(ts), ts
 
 
+def sampling(ks, dev):
+    """--sampling: sample_direction and pdf_direction of a prepared sequence (64 x 256 table)
+    beside sequence.eval of the same n and K in the same session: the fused sampler runs eval's
+    frame loop plus a prologue, so eval is its yardstick.  pdf_direction walks one 16-byte
+    record per frame: reported as frame x directions / s."""
+    g = torch.Generator(device=dev).manual_seed(3)
+    u = torch.rand((2, N), device=dev, generator=g)
+    base = {"type": "sunsky", "sun_direction": [0.3, 0.4, 0.866], "turbidity": 3.0, "albedo": 0.2}
+    for k in ks:
+        dirs, turb, wts = frames(k)
+        seq = ss.SunskySequence(ss.load_dict(dict(base)), dirs, turb, wts)
+        t0 = time.perf_counter()
+        seq.prepare_sampling()
+        t_prep = (time.perf_counter() - t0) * 1e3
+        ds, _ = seq.sample_direction(None, u)
+        wi = (-ds.d).contiguous()
+        out = torch.empty((3, N), device=dev)
+        t_eval, all_eval = median_ms(lambda: seq.eval(wi, out=out))
+        t_samp, all_samp = median_ms(lambda: seq.sample_direction(None, u))
+        t_pdf, all_pdf = median_ms(lambda: seq.pdf_direction(None, ds))
+        info = seq.sampling_info()
+        print(json.dumps({"K": k, "n": N, "table": [info["n_z"], info["n_phi"]], "w_sky": round(info["w_sky"], 4),
+                          "prepare_ms": round(t_prep, 3), "eval_ms": round(t_eval, 3),
+                          "sample_direction_ms": round(t_samp, 3), "sample_over_eval": round(t_samp / t_eval, 3),
+                          "pdf_direction_ms": round(t_pdf, 3),
+                          "pdf_frame_directions_per_s": round(N * k / (t_pdf * 1e-3), 0),
+                          "eval_ms_all": [round(t, 3) for t in all_eval],
+                          "sample_direction_ms_all": [round(t, 3) for t in all_samp],
+                          "pdf_direction_ms_all": [round(t, 3) for t in all_pdf]}), flush=True)
+    print("sequence_bench sampling done")
+
+
 def main():
-    ks = [int(a) for a in sys.argv[1:]] or [24, 365]
+    args = [a for a in sys.argv[1:] if a != "--sampling"]
+    ks = [int(a) for a in args] or [24, 365]
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
+    if "--sampling" in sys.argv[1:]:
+        return sampling(ks, dev)
     g = torch.Generator(device=dev).manual_seed(3)
     v = torch.randn((3, N), device=dev, generator=g)
     v[2] = v[2].abs()
