@@ -19,7 +19,7 @@
  *     eval_direction, eval_spectral_broadcast, sample_direction, pdf_direction,
  *     sample_ray, sample_wavelengths, direct_diffuse, direct_diffuse_rays,
  *     eval_jvp_dir, eval_vjp_dir, sequence_eval, sequence_sample_direction,
- *     sequence_pdf_direction)
+ *     sequence_pdf_direction, sequence_eval_vjp)
  *     allocate nothing, make no host-synchronous call and may be captured into
  *     a hipGraph (tests/test_graph_capture.py).  Kernels read the emitter state
  *     from device memory, which parameters_changed_async rewrites in place on
@@ -53,7 +53,7 @@ extern "C" {
                                         added since, additive only (the version stays 7):
                                         eval_jvp_dir, eval_vjp_dir; sun_coordinates and the
                                         sunsky_sequence_* calls (frame sequences, their
-                                        sampling included) */
+                                        sampling, update and gradients included) */
 
 typedef enum sunsky_status {
     SUNSKY_OK = 0,
@@ -273,8 +273,8 @@ int sunsky_bake_latlong(const sunsky_emitter *e, int width, int height, float th
  * A time-lapse, a cumulative-sky map or a time-averaged sky is one launch instead of one
  * restaging and one pass over the rays per instant.
  * Out of scope: per-ray wavelengths (their channel index is per lane, so a frame's record
- * would no longer be wave-uniform), per-ray frame indices, AD, per-frame albedo / scales /
- * aperture. */
+ * would no longer be wave-uniform), per-ray frame indices, forward-mode AD over a sequence
+ * (the reverse mode is sunsky_sequence_eval_vjp below), per-frame albedo / scales / aperture. */
 typedef struct sunsky_sequence sunsky_sequence;
 typedef struct sunsky_sequence_desc {
     int count;        /* frames                       */
@@ -383,6 +383,65 @@ int sunsky_sequence_sample_direction(const sunsky_sequence *seq, const float *sa
                                      void *stream);
 int sunsky_sequence_pdf_direction(const sunsky_sequence *seq, sunsky_vec3_in ds_d, const uint8_t *active,
                                   size_t n, float *pdf, void *stream);
+
+/* Per-frame gradients of the weighted sum (reverse mode) and the in-place update of the
+ * frames: what fitting the weights, turbidities or sun positions of a sequence needs.
+ * With a cotangent d_out in the layout of sunsky_sequence_eval's out and
+ *     L = sum_i sum_p d_out[p, i] sum_k w_k eval_k(wi_i)[p],
+ * sunsky_sequence_eval_vjp accumulates (+=) into three device arrays, any of which may be NULL:
+ *     grad_weight[k]        += dL/dw_k   = sum_i sum_p d_out eval_k
+ *     grad_turbidity[k]     += dL/dT_k   = w_k sum_i sum_p d_out d eval_k / d T_k
+ *     grad_sun_dir[3 k + a] += dL/ds_k[a] = w_k sum_i sum_p d_out d eval_k / d s_k[a]  (world axis a)
+ * eval_k and its derivatives are those of the single emitter frame k stands for, with
+ * sunsky_eval_vjp's conventions: reference-precision arithmetic whatever the sequence's
+ * precision; the horizon mask, the disc test, the elevation segment and the wavelength validity
+ * are not differentiated; floor(T) is constant with d t_rem / dT = 1 (at T = 10 the masked
+ * upper row behaves as it does there); a sun below the horizon has zero sky tangents; the disc
+ * term is included (T through the sun table's turbidity-lerp slope, taken from the raw dataset
+ * on the spot; s through cos psi).  The sequence normalises s_k, so d / d s_k is the single
+ * emitter's gradient at s_k / |s_k| taken through the normalisation,
+ * (I - s^ s^T) / |s_k| applied before to_world's linear part: it has no component along s_k.
+ * Inactive lanes (mask, cos theta < 0) and invalid wavelengths contribute exactly 0; a frame
+ * with w_k = 0 gets exact zeros in grad_turbidity and grad_sun_dir.  Gradients of the albedo,
+ * the scales and the aperture (the snapshot's, not a frame's) are out of scope.
+ *
+ * sunsky_sequence_update replaces the frames of an existing sequence (the same count; a NULL
+ * array keeps the current values) with sunsky_sequence_create's validation and messages; a
+ * refused update leaves the sequence untouched.  The records are restaged in place by the code
+ * create runs: afterwards get_frame and eval are bit for bit those of a sequence created with
+ * the new values (host-only sequences too).  Host-synchronous, not capturable, not to be called
+ * while launches on the sequence are in flight.  It drops the sampling distribution
+ * (sample_direction / pdf_direction fail as before prepare_sampling until it is called again)
+ * and restages the gradient records if they were prepared.
+ *
+ * sunsky_sequence_prepare_grad (host-synchronous, like prepare_sampling; works on host-only
+ * sequences, staging on the host) stages one gradient record per frame -- the tangents of the
+ * frame's sky tables along T (bit for bit the dsky of sunsky_emitter_tangent_tables(turbidity,
+ * [1]) of its single emitter) and along a unit sun elevation, and per world axis the tangent
+ * of the local sun direction and of the elevation -- and allocates the reduction workspace.
+ * Before it sunsky_sequence_eval_vjp fails with SUNSKY_ERROR_INVALID_VALUE.
+ * sunsky_sequence_get_frame_tangent returns frame k's record (any output may be NULL):
+ * nb_channels x 10 floats d{A..I, rad} each, dsun_local[3 a + r] and deta[a].
+ *
+ * sunsky_sequence_eval_vjp is a hot-path call: stream-ordered, no allocation, no
+ * host-synchronous call, capturable.  Arguments as sunsky_sequence_eval's, and d_out must not
+ * be NULL; n == 0 succeeds and writes nothing.  The reduction is deterministic (wave shuffles,
+ * one row of 5 sums per frame and wave, rows added in a fixed order; no float atomics): two
+ * runs give the same bits.  The workspace belongs to the sequence: calls on one sequence from
+ * different streams are the caller's to order.  It is bounded: one row of count x 5 floats per
+ * workgroup of the launch (count <= 512: the 4 waves' rows are added up in LDS first) or per
+ * wave (count > 512), and the grid is at most 16 workgroups per CU (SUNSKY_AMD_BLOCKS_PER_CU
+ * overrides it) and shrinks as count grows so that the rows take at most 16 MiB -- or one
+ * workgroup's 80 x count bytes where that is more. */
+int sunsky_sequence_update(sunsky_sequence *seq, const float *sun_dirs, const float *turbidity,
+                           const float *weights);
+int sunsky_sequence_prepare_grad(sunsky_sequence *seq);
+int sunsky_sequence_get_frame_tangent(const sunsky_sequence *seq, int k, float *dsky_turbidity,
+                                      float *dsky_elevation, float dsun_local[9], float deta[3]);
+int sunsky_sequence_eval_vjp(const sunsky_sequence *seq, sunsky_vec3_in wi, const float *wavelengths_host,
+                             int n_wavelengths, const uint8_t *active, size_t n, const float *d_out,
+                             size_t out_stride, float *grad_weight, float *grad_turbidity,
+                             float *grad_sun_dir, void *stream);
 
 /* A caller of sample_direction / pdf_direction / eval: the sun-and-sky light a
  * smooth-diffuse point receives, gathered as the path integrator does at one vertex

@@ -450,6 +450,44 @@ public:
                        void* stream = nullptr) const {
         check(sunsky_sequence_pdf_direction(s_, sunsky_vec3_in{ds.d.x, ds.d.y, ds.d.z}, active, n, pdf, stream));
     }
+    // Per-frame gradients of the weighted sum (sunsky_amd.h).  update: empty = keep the current
+    // values; the frame count does not change.
+    struct FrameTangent {
+        std::vector<float> dsky_turbidity, dsky_elevation;   // nb_channels x 10 each
+        float dsun_local[9];                                  // [3 a + r]: d local sun[r] / d s[a]
+        float deta[3];
+    };
+    void update(const std::vector<float>& sun_dirs = {}, const std::vector<float>& turbidity = {},
+                const std::vector<float>& weights = {}) {
+        const size_t k = (size_t)count();
+        if ((!sun_dirs.empty() && sun_dirs.size() != 3 * k) || (!turbidity.empty() && turbidity.size() != k) ||
+            (!weights.empty() && weights.size() != k))
+            throw Error(SUNSKY_ERROR_INVALID_VALUE, "update takes the sequence's frame count: 3 floats per frame of "
+                                                    "sun_dirs, one per frame of turbidity / weights, or none");
+        check(sunsky_sequence_update(s_, sun_dirs.empty() ? nullptr : sun_dirs.data(),
+                                     turbidity.empty() ? nullptr : turbidity.data(),
+                                     weights.empty() ? nullptr : weights.data()));
+    }
+    void prepare_grad() { check(sunsky_sequence_prepare_grad(s_)); }
+    FrameTangent frame_tangent(int k) const {
+        const int nch = info().nb_channels;
+        FrameTangent t;
+        t.dsky_turbidity.resize((size_t)nch * 10);
+        t.dsky_elevation.resize((size_t)nch * 10);
+        check(sunsky_sequence_get_frame_tangent(s_, k, t.dsky_turbidity.data(), t.dsky_elevation.data(), t.dsun_local,
+                                                t.deta));
+        return t;
+    }
+    // += into the device arrays that are not null: grad_weight[count], grad_turbidity[count],
+    // grad_sun_dir[3 count].  d_out: the cotangent, in eval's out layout.
+    void eval_vjp(Vector3 wi, size_t n, const float* d_out, float* grad_weight, float* grad_turbidity,
+                  float* grad_sun_dir, const std::vector<float>& wavelengths = {}, const uint8_t* active = nullptr,
+                  size_t out_stride = 0, void* stream = nullptr) const {
+        check(sunsky_sequence_eval_vjp(s_, sunsky_vec3_in{wi.x, wi.y, wi.z},
+                                       wavelengths.empty() ? nullptr : wavelengths.data(), (int)wavelengths.size(),
+                                       active, n, d_out, out_stride ? out_stride : n, grad_weight, grad_turbidity,
+                                       grad_sun_dir, stream));
+    }
     sunsky_sequence_desc info() const {
         sunsky_sequence_desc d;
         check(sunsky_sequence_info(s_, &d));

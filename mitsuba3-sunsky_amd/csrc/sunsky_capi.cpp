@@ -118,7 +118,9 @@ void check_xform_form(hipModule_t mod, const std::string& path, bool want_identi
 //    r01_v7_tune.log); sample_ray 32, from the sweep over 8/16/32/64
 //    (profiles/r03_v18_kbench_grid_ray_wavelengths.log); 16 where no sweep is recorded.  The
 //    sequence kernels (one ray per lane, bound by VALU issue, not memory) take 64: one step per
-//    lane up to 4M rays, where the cap only bounds the grid.
+//    lane up to 4M rays, where the cap only bounds the grid.  The sequence VJP kernels take 16:
+//    every wave owns a row of the reduction workspace (sunsky_kernel_args.h), so fewer, longer
+//    workgroups keep the workspace and the reduce pass small.
 //  * dir: the eval kernels are instantiated twice: eval(si) negates wi at compile time,
 //    eval_direction(ds) uses ds.d as is (name_dir_fast, name_dir_ref).
 //  * per: samples per work item: 4 consecutive directions per lane in the VEC = 4 kernels
@@ -164,6 +166,8 @@ void check_xform_form(hipModule_t mod, const std::string& path, bool want_identi
     X(SEQUENCE_SAMPLE_RGB, "sunsky_sequence_sample_rgb", 64, false, 1)                             \
     X(SEQUENCE_SAMPLE_SPEC, "sunsky_sequence_sample_spec", 64, false, 1)                           \
     X(SEQUENCE_PDF, "sunsky_sequence_pdf", 64, false, 1)                                           \
+    X(SEQUENCE_EVAL_VJP_RGB, "sunsky_sequence_eval_vjp_rgb", kSeqGradBlocksPerCu, false, 1)        \
+    X(SEQUENCE_EVAL_VJP_SPEC, "sunsky_sequence_eval_vjp_spec", kSeqGradBlocksPerCu, false, 1)      \
     X(DEBUG_SUN_SEGMENTS, "sunsky_debug_sun_segments", 16, false, 1)
 
 #define X(id, name, wg, dir, per) K_##id,
@@ -194,6 +198,7 @@ struct DeviceModule {
     hipFunction_t stage_tangent = nullptr;                                      // eval_jvp / eval_vjp tables
     hipFunction_t stage_sequence = nullptr;                                     // sequence_create
     hipFunction_t sequence_table = nullptr, sequence_suns = nullptr;            // sequence_prepare_sampling
+    hipFunction_t stage_sequence_grad = nullptr, sequence_grad_reduce = nullptr;   // sequence_prepare_grad / _eval_vjp
     int cu_count = 256;
 };
 
@@ -237,6 +242,8 @@ DeviceModule* module_for_device(int dev) {
     get(&m->stage_sequence, m->module, "sunsky_stage_sequence");
     get(&m->sequence_table, m->module, "sunsky_sequence_table");
     get(&m->sequence_suns, m->module, "sunsky_sequence_suns");
+    get(&m->stage_sequence_grad, m->module, "sunsky_stage_sequence_grad");
+    get(&m->sequence_grad_reduce, m->module, "sunsky_sequence_grad_reduce");
     get(&m->stage_radiance, m->module, "sunsky_stage_radiance");
     get(&m->quad_points, m->module, "sunsky_stage_quad_points");
     get(&m->quad_finish, m->module, "sunsky_stage_quad_finish");
@@ -664,9 +671,30 @@ struct sunsky_sequence {
     std::vector<float> samp_f, samp_row_cdf, samp_cell_cdf, samp_q, samp_frame_cdf, samp_B;
     float* d_samp = nullptr;                 // f, row_cdf, cell_cdf, frame_cdf, suns in one block
     SeqSampling samp = {};
+    // what update / prepare_grad restage from: the frames as given (defaults resolved) and the
+    // parent's albedo, to_local and raw sky datasets (host copies for host-only sequences, the
+    // sequence's own device copy otherwise: the parent may be gone)
+    std::vector<float> in_dirs, in_turbidity, in_weights;
+    std::vector<float> albedo;
+    double to_local_d[9] = {0};
+    std::vector<float> h_sky_params_ds, h_sky_rad_ds;
+    float* d_sky_ds = nullptr;               // sky params | sky radiance
+    const float *d_sky_params_ds = nullptr, *d_sky_rad_ds = nullptr;
+    // gradients (prepare_grad): the records' host mirror (frame_tangent), the device records,
+    // the staging scalars and the reduction workspace of the largest grid eval_vjp launches
+    bool grad_ready = false;
+    std::vector<unsigned char> grads;        // SeqGradFrame<nch>[count]
+    void* d_grads = nullptr;
+    TangentStage* d_grad_stages = nullptr;
+    float* d_grad_rows = nullptr;
+    unsigned grad_max_grid = 0;
 
     void require_device() const {
         if (!mod) throw std::invalid_argument("host-only sequence (over a sunsky_emitter_create_host emitter) cannot launch kernels");
+    }
+    void require_grad() const {
+        if (!grad_ready)
+            throw std::invalid_argument("the sequence has no gradient records yet: call sunsky_sequence_prepare_grad first");
     }
     void require_sampling() const {
         if (!samp_nz)
@@ -686,7 +714,8 @@ struct sunsky_sequence {
         int cur = -1;
         if (hipGetDevice(&cur) == hipSuccess && cur != device) (void)hipSetDevice(device);
         (void)hipDeviceSynchronize();   // launches in flight may still read the records
-        for (void* p : {(void*)d_state, d_frames, (void*)d_sun_rad, (void*)d_sun_ld, (void*)d_bake, (void*)d_samp})
+        for (void* p : {(void*)d_state, d_frames, (void*)d_sun_rad, (void*)d_sun_ld, (void*)d_bake, (void*)d_samp,
+                        (void*)d_sky_ds, d_grads, (void*)d_grad_stages, (void*)d_grad_rows})
             if (p) (void)hipFree(p);
         if (bake_done) (void)hipEventDestroy(bake_done);
         if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
@@ -710,16 +739,15 @@ const SkyChannel* seq_sky(const sunsky_sequence* q, int k) {
 // Validation and the per-frame geometry staging from the parent's state: the local sun
 // direction as the emitter's constructor forms it (normalised, then to_local; sunsky.cpp:
 // 923, 176), and the RadianceStage scalars of (its elevation, the frame's turbidity).
-void seq_fill_headers(sunsky_sequence* q, const SunskyModel& model, const float* dirs, const float* turbidity,
-                      const float* weights) {
+void seq_fill_headers(sunsky_sequence* q, const float* dirs, const float* turbidity, const float* weights) {
     for (int k = 0; k < q->count; ++k) {
-        const float T = turbidity ? turbidity[k] : model.turbidity();
+        const float T = turbidity[k];
         if (!(T >= 1.f && T <= 10.f)) {
             char buf[128];
             std::snprintf(buf, sizeof(buf), "Turbidity value %f is out of range [1, 10]", T);
             throw std::invalid_argument(std::string(buf) + " (frame " + std::to_string(k) + ")");
         }
-        const float w = weights ? weights[k] : 1.f;
+        const float w = weights[k];
         if (!std::isfinite(w) || w < 0.f)
             throw std::invalid_argument("frame " + std::to_string(k) + ": the weight must be finite and >= 0");
         const float3_ d = mk3(dirs[3 * k], dirs[3 * k + 1], dirs[3 * k + 2]);
@@ -742,20 +770,132 @@ void seq_fill_headers(sunsky_sequence* q, const SunskyModel& model, const float*
 }
 
 // sunsky_stage_sequence on the host (host-only sequences): the same functions per entry
-void seq_stage_host(sunsky_sequence* q, const SunskyModel& model, float sky_scale) {
+void seq_stage_host(sunsky_sequence* q, float sky_scale) {
     const int nch = q->nch, np = nch * kNbSkyParams;
-    const std::vector<float>& alb = model.albedo();
+    const std::vector<float>& alb = q->albedo;
     std::vector<float> p(np), r(nch);
     for (int k = 0; k < q->count; ++k) {
         const SeqFrame<1>* h = seq_header(q, k);
         const RadianceStage rs = {h->x, h->t_rem, h->t_low, h->t_high, h->in_range};
-        for (int e = 0; e < np; ++e) p[e] = radiance_param(model.sky_params_ds().data(), np, e, rs, alb[e / kNbSkyParams]);
-        for (int e = 0; e < nch; ++e) r[e] = radiance_param(model.sky_rad_ds().data(), nch, e, rs, alb[e]);
+        for (int e = 0; e < np; ++e) p[e] = radiance_param(q->h_sky_params_ds.data(), np, e, rs, alb[e / kNbSkyParams]);
+        for (int e = 0; e < nch; ++e) r[e] = radiance_param(q->h_sky_rad_ds.data(), nch, e, rs, alb[e]);
         unsigned char* rec = q->records.data() + (size_t)k * q->rec_bytes;
         FastChannel* fast = reinterpret_cast<FastChannel*>(rec + kSeqFrameHeader);
         SkyChannel* sky = reinterpret_cast<SkyChannel*>(rec + kSeqFrameHeader + (size_t)nch * sizeof(FastChannel));
         for (int c = 0; c < nch; ++c) fold_channel(&p[c * kNbSkyParams], r[c], q->variant, sky_scale, &sky[c], &fast[c]);
     }
+}
+
+// Headers from q->in_* (validated), then the channels: the one path of create and update, so an
+// updated sequence's records are a new sequence's bits.  Throws before anything on the device
+// or in q->records changes when a frame is refused.
+void seq_restage(sunsky_sequence* q, const std::vector<float>& dirs, const std::vector<float>& turbidity,
+                 const std::vector<float>& weights) {
+    const std::vector<unsigned char> keep = q->records;
+    q->records.assign((size_t)q->count * q->rec_bytes, 0);
+    try {
+        seq_fill_headers(q, dirs.data(), turbidity.data(), weights.data());
+    } catch (...) {
+        q->records = keep;
+        throw;
+    }
+    if (q->device < 0) {
+        seq_stage_host(q, q->kargs.sky_scale);
+        return;
+    }
+    hip_check(hipMemcpy(q->d_frames, q->records.data(), q->records.size(), hipMemcpyHostToDevice), "hipMemcpy");
+    SeqStageArgs A;
+    std::memset(&A, 0, sizeof(A));
+    A.frames = q->d_frames;
+    A.sky_params_ds = q->d_sky_params_ds;
+    A.sky_rad_ds = q->d_sky_rad_ds;
+    for (int c = 0; c < q->nch; ++c) A.albedo[c] = q->albedo[c];
+    A.nch = q->nch;
+    A.variant = q->variant;
+    A.count = q->count;
+    A.sky_scale = q->kargs.sky_scale;
+    void* sargs[] = {&A};
+    hip_check(hipModuleLaunchKernel(q->mod->stage_sequence, (unsigned)std::min(q->count, 65535), 1, 1, 256, 1, 1, 0, nullptr,
+                                    sargs, nullptr), "hipModuleLaunchKernel(sunsky_stage_sequence)");
+    hip_check(hipStreamSynchronize(nullptr), "hipStreamSynchronize");
+    hip_check(hipMemcpy(q->records.data(), q->d_frames, q->records.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+}
+
+// ---- gradient records (sunsky_sequence_prepare_grad)
+float* seq_grad_rec(sunsky_sequence* q, int k) {
+    return reinterpret_cast<float*>(q->grads.data() + (size_t)k * seq_grad_bytes(q->nch));
+}
+const float* seq_grad_rec(const sunsky_sequence* q, int k) {
+    return reinterpret_cast<const float*>(q->grads.data() + (size_t)k * seq_grad_bytes(q->nch));
+}
+
+// Frame k's staging scalars through tangent_stage_for (SunskyModel::tangent_stage's function)
+// with the frame's local sun and turbidity.  s_k = |s| s^ enters the sequence normalised
+// (seq_fill_headers), so the tangent of world axis a is the single emitter's along
+// (I - s^ s^T) e_a / |s|: dlocal[a], deta[a].  Returns the frame's scalars with every tangent
+// 0, from which the staging derives the turbidity and unit-elevation tangents.
+TangentStage seq_grad_header(sunsky_sequence* q, int k) {
+    const SeqFrame<1>* h = seq_header(q, k);
+    const TangentFrame f = {q->to_local_d, h->sun_n, unit_angle_z(mk3(h->sun_n[0], h->sun_n[1], h->sun_n[2])),
+                            h->turbidity, q->nch, q->albedo.data(), false};
+    const double d[3] = {q->in_dirs[3 * (size_t)k], q->in_dirs[3 * (size_t)k + 1], q->in_dirs[3 * (size_t)k + 2]};
+    const double len = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    const double u[3] = {d[0] / len, d[1] / len, d[2] / len};
+    float* g = seq_grad_rec(q, k) + 2 * seq_grad_block(q->nch);
+    for (int a = 0; a < 3; ++a) {
+        float tangent[3];
+        for (int r = 0; r < 3; ++r) tangent[r] = (float)(((r == a ? 1.0 : 0.0) - u[r] * u[a]) / len);
+        const TangentStage s = tangent_stage_for(f, kJvpSunDirection, tangent, 3);
+        for (int r = 0; r < 3; ++r) g[3 * a + r] = s.dsun_local[r];
+        g[9 + a] = (float)s.deta;
+    }
+    const float zero = 0.f;
+    return tangent_stage_for(f, kJvpTurbidity, &zero, 1);
+}
+
+// The gradient records of the current frames: headers on the host, the sky blocks by
+// sunsky_stage_sequence_grad (host-only sequences: the same tangent_value on the host)
+void seq_stage_grad(sunsky_sequence* q) {
+    const int nch = q->nch, block = seq_grad_block(nch);
+    q->grads.assign((size_t)q->count * seq_grad_bytes(nch), 0);
+    std::vector<TangentStage> stages(q->count);
+    for (int k = 0; k < q->count; ++k) stages[k] = seq_grad_header(q, k);
+    if (q->device < 0) {
+        for (int k = 0; k < q->count; ++k) {
+            TangentStage st = stages[k], se = stages[k];
+            st.dT = 1.0;
+            se.dx = se.dx_per_eta;
+            float* g = seq_grad_rec(q, k);
+            for (int j = 0; j < nch * 10; ++j) {
+                g[j] = tangent_value(q->h_sky_params_ds.data(), q->h_sky_rad_ds.data(), st, j);
+                g[block + j] = tangent_value(q->h_sky_params_ds.data(), q->h_sky_rad_ds.data(), se, j);
+            }
+        }
+        return;
+    }
+    hip_check(hipMemcpy(q->d_grads, q->grads.data(), q->grads.size(), hipMemcpyHostToDevice), "hipMemcpy");
+    hip_check(hipMemcpy(q->d_grad_stages, stages.data(), sizeof(TangentStage) * stages.size(), hipMemcpyHostToDevice),
+              "hipMemcpy");
+    SeqGradStageArgs A = {q->d_grads, q->d_grad_stages, q->d_sky_params_ds, q->d_sky_rad_ds, nch, q->count};
+    void* args[] = {&A};
+    hip_check(hipModuleLaunchKernel(q->mod->stage_sequence_grad, (unsigned)std::min(q->count, 65535), 1, 1, 256, 1, 1, 0,
+                                    nullptr, args, nullptr), "hipModuleLaunchKernel(sunsky_stage_sequence_grad)");
+    hip_check(hipStreamSynchronize(nullptr), "hipStreamSynchronize");
+    hip_check(hipMemcpy(q->grads.data(), q->d_grads, q->grads.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+}
+
+// Workspace rows per workgroup of sunsky_sequence_eval_vjp: one while the waves' rows live in
+// LDS (the workgroup adds them up), one per wave otherwise
+size_t seq_grad_rows_per_block(const sunsky_sequence* q) {
+    return q->count <= kSeqGradLdsFrames ? 1 : kBlock / 64;
+}
+
+// The grid of sunsky_sequence_eval_vjp over n rays: the kernel table's cap, then the
+// workspace bound (rows of count x 5 floats)
+unsigned seq_grad_grid(const sunsky_sequence* q, size_t n) {
+    const size_t row = (size_t)q->count * kSeqGradSums * seq_grad_rows_per_block(q);
+    const size_t cap = std::max<size_t>(1, kSeqGradWorkspaceFloats / row);
+    return (unsigned)std::min<size_t>(grid_for(q->mod, K_SEQUENCE_EVAL_VJP_RGB, n), cap);
 }
 
 // ---- sampling tables (sunsky_sequence_prepare_sampling)
@@ -1651,13 +1791,21 @@ int sunsky_sequence_create(const sunsky_emitter* e, int count, const float* sun_
         q->precision = e->precision;
         q->sun_block = q->variant == kSpectral ? kSunSpecTableSize : kSunRgbTableSize;
         q->rec_bytes = kSeqFrameHeader + (size_t)q->nch * (sizeof(FastChannel) + sizeof(SkyChannel));
-        q->records.assign((size_t)count * q->rec_bytes, 0);
-        seq_fill_headers(q.get(), model, sun_dirs, turbidity, weights);
         std::memcpy(q->cie_y, model.cie_y(), sizeof(q->cie_y));
+        // the frames as given, defaults resolved: what sunsky_sequence_update keeps for a NULL array
+        std::vector<float> dirs(sun_dirs, sun_dirs + 3 * (size_t)count);
+        std::vector<float> T(count, model.turbidity()), w(count, 1.f);
+        if (turbidity) T.assign(turbidity, turbidity + count);
+        if (weights) w.assign(weights, weights + count);
+        q->albedo = model.albedo();
+        std::memcpy(q->to_local_d, model.to_local_d(), sizeof(q->to_local_d));
         if (e->device < 0) {
             q->h_sun_rad = model.sun_rad_ds();   // prepare_sampling's disc term on the host
             q->h_sun_ld = model.sun_ld();
-            seq_stage_host(q.get(), model, q->kargs.sky_scale);
+            q->h_sky_params_ds = model.sky_params_ds();
+            q->h_sky_rad_ds = model.sky_rad_ds();
+            seq_restage(q.get(), dirs, T, w);
+            q->in_dirs = std::move(dirs); q->in_turbidity = std::move(T); q->in_weights = std::move(w);
             *out = q.release();
             return;
         }
@@ -1667,34 +1815,132 @@ int sunsky_sequence_create(const sunsky_emitter* e, int count, const float* sun_
         q->device = e->device;
         const std::vector<float>& su = model.sun_rad_ds();
         const std::vector<float>& ld = model.sun_ld();
-        hip_check(hipMalloc(&q->d_frames, q->records.size()), "hipMalloc");
+        const std::vector<float>& sp = model.sky_params_ds();
+        const std::vector<float>& sr = model.sky_rad_ds();
+        hip_check(hipMalloc(&q->d_frames, (size_t)count * q->rec_bytes), "hipMalloc");
         hip_check(hipMalloc(&q->d_sun_rad, sizeof(float) * su.size()), "hipMalloc");
         hip_check(hipMalloc(&q->d_sun_ld, sizeof(float) * kNbWavelengths * kNbSunLdParams), "hipMalloc");
         hip_check(hipMalloc(&q->d_state, sizeof(SunskyKArgs)), "hipMalloc");
-        hip_check(hipMemcpy(q->d_frames, q->records.data(), q->records.size(), hipMemcpyHostToDevice), "hipMemcpy");
+        hip_check(hipMalloc(&q->d_sky_ds, sizeof(float) * (sp.size() + sr.size())), "hipMalloc");
         hip_check(hipMemcpy(q->d_sun_rad, su.data(), sizeof(float) * su.size(), hipMemcpyHostToDevice), "hipMemcpy");
         hip_check(hipMemset(q->d_sun_ld, 0, sizeof(float) * kNbWavelengths * kNbSunLdParams), "hipMemset");
         hip_check(hipMemcpy(q->d_sun_ld, ld.data(), sizeof(float) * std::min<size_t>(ld.size(), kNbWavelengths * kNbSunLdParams),
                             hipMemcpyHostToDevice), "hipMemcpy");
+        // the raw sky datasets, the sequence's own copy: update restages from it when the parent is gone
+        hip_check(hipMemcpy(q->d_sky_ds, sp.data(), sizeof(float) * sp.size(), hipMemcpyHostToDevice), "hipMemcpy");
+        hip_check(hipMemcpy(q->d_sky_ds + sp.size(), sr.data(), sizeof(float) * sr.size(), hipMemcpyHostToDevice), "hipMemcpy");
+        q->d_sky_params_ds = q->d_sky_ds;
+        q->d_sky_rad_ds = q->d_sky_ds + sp.size();
         q->kargs.sun_ld = q->d_sun_ld;
         hip_check(hipMemcpy(q->d_state, &q->kargs, sizeof(SunskyKArgs), hipMemcpyHostToDevice), "hipMemcpy");
-        SeqStageArgs A;
-        std::memset(&A, 0, sizeof(A));
-        A.frames = q->d_frames;
-        A.sky_params_ds = e->d_sky_params_ds;
-        A.sky_rad_ds = e->d_sky_rad_ds;
-        const std::vector<float>& alb = model.albedo();
-        for (int c = 0; c < q->nch; ++c) A.albedo[c] = alb[c];
-        A.nch = q->nch;
-        A.variant = q->variant;
-        A.count = count;
-        A.sky_scale = q->kargs.sky_scale;
-        void* sargs[] = {&A};
-        hip_check(hipModuleLaunchKernel(q->mod->stage_sequence, (unsigned)std::min(count, 65535), 1, 1, 256, 1, 1, 0, nullptr,
-                                        sargs, nullptr), "hipModuleLaunchKernel(sunsky_stage_sequence)");
-        hip_check(hipStreamSynchronize(nullptr), "hipStreamSynchronize");
-        hip_check(hipMemcpy(q->records.data(), q->d_frames, q->records.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+        seq_restage(q.get(), dirs, T, w);
+        q->in_dirs = std::move(dirs); q->in_turbidity = std::move(T); q->in_weights = std::move(w);
         *out = q.release();
+    });
+}
+
+int sunsky_sequence_update(sunsky_sequence* seq, const float* sun_dirs, const float* turbidity, const float* weights) {
+    SUNSKY_PHASE("InitScene", "sequence_update");
+    if (!seq) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sequence");
+    return guarded([&] {
+        const size_t K = (size_t)seq->count;
+        std::vector<float> dirs = seq->in_dirs, T = seq->in_turbidity, w = seq->in_weights;
+        if (sun_dirs) dirs.assign(sun_dirs, sun_dirs + 3 * K);
+        if (turbidity) T.assign(turbidity, turbidity + K);
+        if (weights) w.assign(weights, weights + K);
+        std::unique_ptr<DeviceScope> g;
+        if (seq->device >= 0) {
+            g.reset(new DeviceScope(seq->device));
+            hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");   // nothing may still read the old records
+        }
+        seq_restage(seq, dirs, T, w);   // throws with the sequence untouched when a frame is refused
+        seq->in_dirs = std::move(dirs); seq->in_turbidity = std::move(T); seq->in_weights = std::move(w);
+        // the sampling distribution described the old frames
+        seq->samp_nz = seq->samp_nphi = 0;
+        if (seq->grad_ready) seq_stage_grad(seq);
+    });
+}
+
+int sunsky_sequence_prepare_grad(sunsky_sequence* seq) {
+    SUNSKY_PHASE("InitScene", "sequence_prepare_grad");
+    if (!seq) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sequence");
+    return guarded([&] {
+        std::unique_ptr<DeviceScope> g;
+        if (seq->device >= 0) {
+            g.reset(new DeviceScope(seq->device));
+            hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");   // nothing may still read the old records
+            if (!seq->d_grad_rows) {   // once: the records, the staging scalars, the rows of the largest grid
+                seq->grad_max_grid = seq_grad_grid(seq, ~(size_t)0 / 2);
+                const size_t rows = (size_t)seq->grad_max_grid * seq_grad_rows_per_block(seq);
+                if (!seq->d_grads) hip_check(hipMalloc(&seq->d_grads, (size_t)seq->count * seq_grad_bytes(seq->nch)), "hipMalloc");
+                if (!seq->d_grad_stages)
+                    hip_check(hipMalloc(&seq->d_grad_stages, sizeof(TangentStage) * (size_t)seq->count), "hipMalloc");
+                hip_check(hipMalloc(&seq->d_grad_rows, sizeof(float) * rows * (size_t)seq->count * kSeqGradSums), "hipMalloc");
+            }
+        }
+        seq_stage_grad(seq);
+        seq->grad_ready = true;
+    });
+}
+
+int sunsky_sequence_get_frame_tangent(const sunsky_sequence* seq, int k, float* dsky_turbidity, float* dsky_elevation,
+                                      float dsun_local[9], float deta[3]) {
+    if (!seq) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sequence");
+    if (k < 0 || k >= seq->count) return fail(SUNSKY_ERROR_INVALID_VALUE, "frame index out of range");
+    return guarded([&] {
+        seq->require_grad();
+        const int block = seq_grad_block(seq->nch);
+        const float* g = seq_grad_rec(seq, k);
+        const size_t sky = sizeof(float) * (size_t)seq->nch * 10;
+        if (dsky_turbidity) std::memcpy(dsky_turbidity, g, sky);
+        if (dsky_elevation) std::memcpy(dsky_elevation, g + block, sky);
+        if (dsun_local) std::memcpy(dsun_local, g + 2 * block, 9 * sizeof(float));
+        if (deta) std::memcpy(deta, g + 2 * block + 9, 3 * sizeof(float));
+    });
+}
+
+int sunsky_sequence_eval_vjp(const sunsky_sequence* seq, sunsky_vec3_in wi, const float* lam_host, int m,
+                             const uint8_t* active, size_t n, const float* d_out, size_t ostride, float* grad_weight,
+                             float* grad_turbidity, float* grad_sun_dir, void* stream) {
+    SUNSKY_PHASE("EndpointEvaluate", "sequence_eval_vjp");
+    if (!seq) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sequence");
+    const bool spec = seq->variant == kSpectral;
+    if (spec && (!lam_host || m < 1 || m > kMaxBroadcastLambda))
+        return fail(SUNSKY_ERROR_INVALID_VALUE, "1..32 broadcast wavelengths required for a spectral sequence");
+    if (!spec && lam_host && m) return fail(SUNSKY_ERROR_INVALID_VALUE, "an RGB sequence takes no wavelengths");
+    if (n == 0) return SUNSKY_OK;
+    if (!wi.x || !wi.y || !wi.z) return fail(SUNSKY_ERROR_INVALID_VALUE, "null ray pointer");
+    if (!d_out) return fail(SUNSKY_ERROR_INVALID_VALUE, "null cotangent (d_out)");
+    if ((spec ? m : 3) > 1 && ostride < n) return fail(SUNSKY_ERROR_INVALID_VALUE, "out_stride < n");
+    return guarded([&] {
+        seq->require_grad();   // first: the message names the missing call on any sequence
+        seq->require_device();
+        if (!grad_weight && !grad_turbidity && !grad_sun_dir) return;
+        DeviceScope g(seq->device);
+        hipStream_t s = (hipStream_t)stream;
+        const unsigned grid = seq_grad_grid(seq, n);   // <= grad_max_grid: the workspace holds its rows
+        const bool lds = seq->count <= kSeqGradLdsFrames;
+        const SunskyKArgs* K = seq->d_state;
+        SeqArgs A = seq->args();
+        SeqGradArgs G = {seq->d_grads, d_out, ostride, seq->d_grad_rows, lds ? 1 : 0, 0};
+        const unsigned dyn = lds ? (unsigned)(sizeof(float) * (kBlock / 64) * (size_t)seq->count * kSeqGradSums) : 0u;
+        // reference arithmetic whatever the sequence's precision: both names run the same body
+        const auto& fns = seq->mod->fn[seq->xform_form()][SUNSKY_PRECISION_REFERENCE];
+        if (!spec) {
+            void* args[] = {&K, &A, &G, (void*)&wi.x, (void*)&wi.y, (void*)&wi.z, &active, &n};
+            launch(fns[K_SEQUENCE_EVAL_VJP_RGB], grid, s, args, dyn);
+        } else {
+            LambdaSet L = make_lambda_set(lam_host, m);
+            void* args[] = {&K, &A, &G, &L, (void*)&wi.x, (void*)&wi.y, (void*)&wi.z, &active, &n};
+            launch(fns[K_SEQUENCE_EVAL_VJP_SPEC], grid, s, args, dyn);
+        }
+        const float* rows = seq->d_grad_rows;
+        unsigned nrows = grid * (unsigned)seq_grad_rows_per_block(seq);
+        int count = seq->count;
+        void* rargs[] = {(void*)&rows, &nrows, &count, &grad_weight, &grad_turbidity, &grad_sun_dir};
+        hip_check(hipModuleLaunchKernel(seq->mod->sequence_grad_reduce, (unsigned)std::min(count, 65535), 1, 1,
+                                        kSeqGradReduceBlock, 1, 1, 0, s, rargs, nullptr),
+                  "hipModuleLaunchKernel(sunsky_sequence_grad_reduce)");
     });
 }
 

@@ -95,7 +95,7 @@ static_assert(offsetof(SeqFrame<3>, weight) == 12 && offsetof(SeqFrame<3>, t_rem
 // sunsky_stage_sequence: one workgroup per frame
 struct SeqStageArgs {
     void* frames;                  // SeqFrame<nch>[count], headers filled
-    const float* sky_params_ds;    // the parent emitter's device datasets (read at creation only)
+    const float* sky_params_ds;    // the raw sky datasets: the sequence's own device copy (create and update)
     const float* sky_rad_ds;
     float albedo[kNbWavelengths];
     int nch, variant, count;
@@ -110,6 +110,64 @@ struct SeqArgs {
     int count, sun_block;
 };
 static_assert(sizeof(SeqArgs) == 24, "SeqArgs layout");
+
+// ---------------------------------------------------------------- sequence gradients
+// One frame's gradient record (sunsky_sequence_prepare_grad; NCH = 3 RGB, 11 spectral): the
+// tangents of the frame's staged tables that sunsky_sequence_eval_vjp contracts per ray.  The
+// host fills dlocal / deta (tangent_stage_for) and sunsky_stage_sequence_grad writes the two sky
+// blocks in place (tangent_value, fp64).  Every block starts on 16 bytes: the kernels read a
+// record with one address per wave, as they read SeqFrame.
+constexpr int seq_grad_block(int nch) { return (nch * 10 + 3) & ~3; }   // 32 RGB, 112 spectral
+template <int NCH>
+struct alignas(16) SeqGradFrame {
+    float dsky_T[seq_grad_block(NCH)];     // d{A..I, rad} / dT per channel (c x 10 + q), floor(T) constant
+    float dsky_eta[seq_grad_block(NCH)];   // ... / d eta: the unit-elevation tangent
+    float dlocal[3][3];                    // d local sun direction / d s[a] (world axis a): normalisation and to_local folded in
+    float deta[3];                         // d eta / d s[a]
+};
+static_assert(sizeof(SeqGradFrame<3>) == 4 * (2 * 32 + 12) && sizeof(SeqGradFrame<kNbWavelengths>) == 4 * (2 * 112 + 12),
+              "SeqGradFrame layout");
+static_assert(offsetof(SeqGradFrame<3>, dsky_eta) == 128 && offsetof(SeqGradFrame<3>, dlocal) == 256 &&
+              offsetof(SeqGradFrame<3>, deta) == 292 && offsetof(SeqGradFrame<kNbWavelengths>, dsky_eta) == 448 &&
+              offsetof(SeqGradFrame<kNbWavelengths>, dlocal) == 896 && offsetof(SeqGradFrame<kNbWavelengths>, deta) == 932,
+              "SeqGradFrame layout");
+static_assert(sizeof(SeqGradFrame<3>) % 16 == 0 && sizeof(SeqGradFrame<kNbWavelengths>) % 16 == 0, "SeqGradFrame alignment");
+constexpr size_t seq_grad_bytes(int nch) { return 4 * (size_t)(2 * seq_grad_block(nch) + 12); }
+
+// sunsky_stage_sequence_grad: one workgroup per frame.  stages[k]: frame k's TangentStage
+// scalars with every tangent 0 (tangent_stage_for); the kernel derives the turbidity tangent
+// (dT = 1) and the unit-elevation tangent (dx = dx_per_eta) from it.
+struct SeqGradStageArgs {
+    void* grads;                   // SeqGradFrame<nch>[count], dlocal / deta filled
+    const TangentStage* stages;    // [count], device
+    const float* sky_params_ds;    // the sequence's own device copy of the sky datasets
+    const float* sky_rad_ds;
+    int nch, count;
+};
+static_assert(sizeof(SeqGradStageArgs) == 40, "SeqGradStageArgs layout");
+
+// The reverse-mode kernels' launch shape.  Each wave keeps one row of 5 sums per frame
+// (weight, turbidity, sun x / y / z): in LDS while count <= kSeqGradLdsFrames (4 waves x count
+// x 5 floats of dynamic LDS, 40 KiB at the limit), added into one row per workgroup at the end;
+// otherwise directly in the workspace, one row per wave.  The workspace is rows x count x 5
+// floats; the grid is capped so that it stays within kSeqGradWorkspaceFloats (and never below
+// one workgroup: 4 rows, 20 x count floats, once count > kSeqGradLdsFrames).
+constexpr int kSeqGradSums = 5;
+constexpr int kSeqGradLdsFrames = 512;
+constexpr size_t kSeqGradWorkspaceFloats = (size_t)1 << 22;   // 16 MiB
+constexpr int kSeqGradBlocksPerCu = 16;
+constexpr int kSeqGradReduceBlock = 64;
+
+// sunsky_sequence_eval_vjp_*: the gradient records, the cotangent and the workspace
+struct SeqGradArgs {
+    const void* grads;             // SeqGradFrame<nch>[count]
+    const float* dout;             // cotangent planes
+    size_t dstride;
+    float* rows;                   // workspace [gridDim.x (LDS rows) or gridDim.x * 4][count][5]
+    int lds_rows;                  // 1: the waves' rows live in dynamic LDS until the end
+    int pad;
+};
+static_assert(sizeof(SeqGradArgs) == 40, "SeqGradArgs layout");
 
 // ---------------------------------------------------------------- sequence sampling
 // The sampling distribution of a sequence (sunsky_sequence_prepare_sampling), all in the

@@ -721,7 +721,7 @@ void SunskyModel::validate() const {
         if (a < 0.f || a > 1.f) throw std::invalid_argument(fmt("Albedo values must be in [0, 1], got: %f", a));
 }
 
-TangentStage SunskyModel::tangent_stage(int param, const float* tangent, int count) const {
+TangentStage tangent_stage_for(const TangentFrame& f, int param, const float* tangent, int count) {
     if (!tangent) throw std::invalid_argument("null tangent");
     TangentStage s;
     std::memset(&s, 0, sizeof(s));
@@ -732,22 +732,22 @@ TangentStage SunskyModel::tangent_stage(int param, const float* tangent, int cou
             s.dT = tangent[0];
             break;
         case kJvpAlbedo:
-            if (count != 1 && count != nch_)
-                throw std::invalid_argument("albedo tangent has 1 or " + std::to_string(nch_) + " values");
-            for (int c = 0; c < nch_; ++c) s.dalbedo[c] = tangent[count == 1 ? 0 : c];
+            if (count != 1 && count != f.nch)
+                throw std::invalid_argument("albedo tangent has 1 or " + std::to_string(f.nch) + " values");
+            for (int c = 0; c < f.nch; ++c) s.dalbedo[c] = tangent[count == 1 ? 0 : c];
             break;
         case kJvpSunDirection: {
-            if (active_record_) throw std::invalid_argument("sun_direction is not differentiable in time/location mode");
+            if (f.active_record) throw std::invalid_argument("sun_direction is not differentiable in time/location mode");
             if (count != 3) throw std::invalid_argument("sun_direction tangent has 3 values");
             // local = M^-1 m_sun_dir (parameters_changed, sunsky.cpp:258-263)
             double dl[3];
             for (int r = 0; r < 3; ++r)
-                dl[r] = to_local_d_[r * 3] * tangent[0] + to_local_d_[r * 3 + 1] * tangent[1] +
-                        to_local_d_[r * 3 + 2] * tangent[2];
+                dl[r] = f.to_local_d[r * 3] * tangent[0] + f.to_local_d[r * 3 + 1] * tangent[1] +
+                        f.to_local_d[r * 3 + 2] * tangent[2];
             for (int r = 0; r < 3; ++r) s.dsun_local[r] = (float)dl[r];
             // theta = unit_angle_z(local) (from_spherical, sunsky.h:84-89); eta = pi/2 - theta
-            const double lz = k_.sun_n[2];
-            const double w[3] = {k_.sun_n[0], k_.sun_n[1], lz - (std::signbit(lz) ? -1.0 : 1.0)};
+            const double lz = f.sun_n[2];
+            const double w[3] = {f.sun_n[0], f.sun_n[1], lz - (std::signbit(lz) ? -1.0 : 1.0)};
             const double h = 0.5 * std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
             if (h > 0.0) {
                 const double dtemp = (w[0] * dl[0] + w[1] * dl[1] + w[2] * dl[2]) / (2.0 * h * std::sqrt(1.0 - h * h));
@@ -760,18 +760,23 @@ TangentStage SunskyModel::tangent_stage(int param, const float* tangent, int cou
     }
     // the staging scalars of compute_radiance_params (sunsky.h:158-231) and their tangents:
     // x = cbrt(2 eta / pi), dx = 2 / (3 pi x^2) deta; t_rem = T - floor(T), d t_rem / dT = 1
-    const float eta = 0.5f * kPi - k_.sun_theta;
+    const float eta = 0.5f * kPi - f.sun_theta;
     s.x = std::cbrt(2.0 * eta / 3.14159265358979323846);
     s.deta = deta;
     s.dx_per_eta = s.x > 0.0 ? (2.0 / (3.0 * 3.14159265358979323846)) / (s.x * s.x) : 0.0;
     s.dx = s.x > 0.0 ? s.dx_per_eta * deta : 0.0;
-    s.t_high = (int)std::floor(turbidity_);
+    s.t_high = (int)std::floor(f.turbidity);
     s.t_low = s.t_high - 1;
-    s.t_rem = (double)turbidity_ - s.t_high;
+    s.t_rem = (double)f.turbidity - s.t_high;
     s.in_range = (0.f <= eta) && (eta <= 0.5f * kPi);
-    s.nch = nch_;
-    for (int c = 0; c < nch_; ++c) s.albedo[c] = albedo_[c];
+    s.nch = f.nch;
+    for (int c = 0; c < f.nch; ++c) s.albedo[c] = f.albedo[c];
     return s;
+}
+
+TangentStage SunskyModel::tangent_stage(int param, const float* tangent, int count) const {
+    const TangentFrame f = {to_local_d_, k_.sun_n, k_.sun_theta, turbidity_, nch_, albedo_.data(), active_record_};
+    return tangent_stage_for(f, param, tangent, count);
 }
 
 EvalTangent SunskyModel::eval_tangent(int param, const float* tangent, int count) const {

@@ -23,6 +23,21 @@ void compute_sun_coordinates(const DateTime& t, const Location& l, float out[3])
 // angle sun_theta (local frame) and a turbidity: the emitter's own staging and every frame
 // of a sequence compute them here, so a frame's staged channels are its emitter's bits.
 RadianceStage radiance_stage_for(float sun_theta, float turbidity);
+// What a tangent of the staging depends on: the state of one emitter, or of one frame of a
+// sequence over the parent's snapshot (its own local sun direction and turbidity).
+struct TangentFrame {
+    const double* to_local_d;   // 3 x 3, row-major: the linear part of to_world^-1
+    const float* sun_n;         // local sun direction
+    float sun_theta;            // unit_angle_z(sun_n)
+    float turbidity;
+    int nch;
+    const float* albedo;        // nch values
+    bool active_record;         // time/location mode: sun_direction is not differentiable
+};
+// The scalars of the staging's tangent along `tangent` of `param` (JvpParam; validates param /
+// count): SunskyModel::tangent_stage for an emitter, every frame of a sequence's gradient
+// records -- one definition, so a frame's tangent tables are its single emitter's bits.
+TangentStage tangent_stage_for(const TangentFrame& f, int param, const float* tangent, int count);
 // quad::gauss_legendre, quad.h:27-86 (fp64 nodes/weights)
 void gauss_legendre(int n, std::vector<double>* nodes, std::vector<double>* weights);
 
@@ -69,6 +84,7 @@ public:
     bool active_record() const { return active_record_; }
     const float* sun_dir_world() const { return sun_dir_; }
     float turbidity() const { return turbidity_; }
+    const double* to_local_d() const { return to_local_d_; }   // 3 x 3 linear part of to_world^-1
     const std::vector<float>& albedo() const { return albedo_; }
     const std::vector<float>& sky_params() const { return sky_params_; }
     const std::vector<float>& sky_radiance() const { return sky_rad_; }

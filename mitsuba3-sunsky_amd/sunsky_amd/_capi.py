@@ -63,6 +63,9 @@ class SequenceSamplingDesc(C.Structure):
 
 
 SEQUENCE_TABLES = {"sky": 0, "row_cdf": 1, "cell_cdf": 2, "q": 3, "frame_cdf": 4, "B": 5}
+# sunsky_sequence_eval_vjp's launch shape (csrc/sunsky_kernel_args.h): workgroups per CU, the
+# workspace bound in floats, the frame count up to which a wave's row lives in LDS
+SEQ_GRAD_BLOCKS_PER_CU, SEQ_GRAD_WORKSPACE_FLOATS, SEQ_GRAD_LDS_FRAMES = 16, 1 << 22, 512
 
 _SIGS = {
     "sunsky_abi_version": (C.c_int, []),
@@ -120,6 +123,11 @@ _SIGS = {
     "sunsky_sequence_sample_direction": (C.c_int, [vp, vp, vp, Vec3In, c_float_p, C.c_int, vp, C.c_size_t, Vec3Out,
                                                    vp, vp, Vec3Out, vp, C.c_size_t, vp]),
     "sunsky_sequence_pdf_direction": (C.c_int, [vp, Vec3In, vp, C.c_size_t, vp, vp]),
+    "sunsky_sequence_update": (C.c_int, [vp, c_float_p, c_float_p, c_float_p]),
+    "sunsky_sequence_prepare_grad": (C.c_int, [vp]),
+    "sunsky_sequence_get_frame_tangent": (C.c_int, [vp, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p]),
+    "sunsky_sequence_eval_vjp": (C.c_int, [vp, Vec3In, c_float_p, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp,
+                                           vp]),
     "sunsky_direct_diffuse": (C.c_int, [vp, Vec3In, vp, vp, C.c_int, C.c_size_t, C.c_uint32, C.c_uint32,
                                         vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp]),
     "sunsky_direct_diffuse_rays": (C.c_int, [vp, Vec3In, C.c_uint32, C.c_uint32, C.c_size_t, Vec3Out, Vec3Out,

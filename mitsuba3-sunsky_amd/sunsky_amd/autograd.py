@@ -1,4 +1,5 @@
-"""torch.autograd bridge for the ray direction of eval().
+"""torch.autograd bridges: the ray direction of eval() (eval_wi) and the per-frame
+parameters of a frame sequence (sequence_eval).
 
 eval_wi(em, wi, ...) is em.eval(si) as a differentiable function of wi: the forward value is
 the emitter's own eval kernel (FAST or reference, whichever the emitter is set to), the
@@ -9,6 +10,12 @@ gradients (turbidity, albedo, sun_direction) stay with SunskyEmitter.eval_vjp.  
 reads the emitter state current when backward() runs, not a snapshot taken at the forward:
 do not update the emitter between the two.  The backward is once_differentiable (there are
 no second derivatives).
+
+sequence_eval(seq, wi, weights, turbidity, sun_directions, ...) is seq.eval(wi) as a
+differentiable function of the frames: the forward writes the given tensors' values into the
+sequence (seq.update, host-synchronous) and evaluates it, the backward is seq.eval_vjp.  The
+same caveats hold: the backward reads the sequence as it is when backward() runs, so do not
+update it (or call sequence_eval on it again) between a forward and its backward.
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -42,3 +49,47 @@ def eval_wi(em, wi, wavelengths=None, active=None):
     if isinstance(wavelengths, torch.Tensor):
         wavelengths = wavelengths.detach()
     return _EvalWi.apply(wi, em, wavelengths, active)
+
+
+class _SequenceEval(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, wi, seq, wavelengths, active, weights, turbidity, sun_directions):
+        wi = wi.detach()
+        ctx.seq, ctx.wavelengths, ctx.active = seq, wavelengths, active
+        ctx.save_for_backward(wi)
+        ctx.devices = [t.device if t is not None else None for t in (weights, turbidity, sun_directions)]
+        if any(ctx.needs_input_grad[4:7]) and not seq.grad_prepared:
+            seq.prepare_grad()   # the update below restages the records
+        if weights is not None or turbidity is not None or sun_directions is not None:
+            seq.update(sun_directions, turbidity, weights)
+        return seq.eval(wi, wavelengths, active)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_out):
+        (wi,) = ctx.saved_tensors
+        seq = ctx.seq
+        keys = ("weights", "turbidity", "sun_directions")
+        need = dict(zip(keys, ctx.needs_input_grad[4:7]))
+        k = len(seq)
+        grad = {key: torch.zeros((k, 3) if key == "sun_directions" else (k,), dtype=torch.float32, device=seq.device)
+                if need[key] else None for key in keys}
+        if any(need.values()):
+            seq.eval_vjp(wi, d_out.contiguous(), ctx.wavelengths, ctx.active, grad=grad)
+        return (None, None, None, None) + tuple(None if grad[key] is None else grad[key].to(dev)
+                                                for key, dev in zip(keys, ctx.devices))
+
+
+def sequence_eval(seq, wi, weights=None, turbidity=None, sun_directions=None, wavelengths=None, active=None):
+    """seq.eval(wi, wavelengths, active), differentiable in the per-frame tensors passed.
+
+    weights (K,), turbidity (K,), sun_directions (K, 3): float32 tensors (any device; their
+    values are read on the host) or None to leave that part of the sequence as it is.  The
+    forward calls seq.update with them and returns bit for bit seq.eval's value; the backward
+    returns gradients for exactly the tensors passed, on each tensor's device.  wi gets none."""
+    if not isinstance(wi, torch.Tensor) or wi.dtype != torch.float32 or wi.dim() != 2 or wi.shape[0] != 3:
+        raise ValueError("wi must be a float32 tensor of shape (3, n)")
+    for name, t in (("weights", weights), ("turbidity", turbidity), ("sun_directions", sun_directions)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32):
+            raise ValueError(f"{name} must be a float32 tensor or None")
+    return _SequenceEval.apply(wi, seq, wavelengths, active, weights, turbidity, sun_directions)

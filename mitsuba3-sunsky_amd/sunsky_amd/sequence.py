@@ -44,27 +44,37 @@ class SunskySequence:
 
     def __init__(self, em, sun_directions, turbidity=None, weights=None):
         self._h = None
-        d = np.ascontiguousarray(np.asarray(sun_directions, dtype=np.float32))
-        if d.ndim != 2 or d.shape[1] != 3:
-            raise ValueError("sun_directions must have shape (K, 3)")
+        self.grad_prepared = False
+        d = self._dirs(sun_directions)
         k = d.shape[0]
-
-        def per_frame(v, name):
-            if v is None:
-                return None
-            a = np.asarray(v, dtype=np.float32)
-            if a.ndim == 0:
-                a = np.full(k, a, dtype=np.float32)
-            if a.shape != (k,):
-                raise ValueError(f"{name} must have {k} values (one per frame), got shape {a.shape}")
-            return _fa(a.tolist())
-
-        t, w = per_frame(turbidity, "turbidity"), per_frame(weights, "weights")
+        t, w = self._per_frame(turbidity, k, "turbidity"), self._per_frame(weights, k, "weights")
         self.device = em.device
         self.variant, self.is_spectral = em.variant, em.is_spectral
         h = C.c_void_p()
         check(lib().sunsky_sequence_create(em._h, k, _fa(d.reshape(-1).tolist()), t, w, C.byref(h)))
         self._h = h
+
+    @staticmethod
+    def _dirs(v):
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        d = np.ascontiguousarray(np.asarray(v, dtype=np.float32))
+        if d.ndim != 2 or d.shape[1] != 3:
+            raise ValueError("sun_directions must have shape (K, 3)")
+        return d
+
+    @staticmethod
+    def _per_frame(v, k, name):
+        if v is None:
+            return None
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        a = np.asarray(v, dtype=np.float32)
+        if a.ndim == 0:
+            a = np.full(k, a, dtype=np.float32)
+        if a.shape != (k,):
+            raise ValueError(f"{name} must have {k} values (one per frame), got shape {a.shape}")
+        return _fa(a.tolist())
 
     @classmethod
     def from_times(cls, em, times, latitude=35.6894, longitude=139.6917, timezone=9.0, turbidity=None, weights=None):
@@ -218,6 +228,76 @@ class SunskySequence:
         out = torch.empty(n, dtype=torch.float32, device=self.device)
         check(lib().sunsky_sequence_pdf_direction(self._h, vin, _ptr(mask), n, _ptr(out), self._stream()))
         return out
+
+    # ------------------------------------------------------------ gradients and updates
+    def update(self, sun_directions=None, turbidity=None, weights=None):
+        """Replaces the frames in place (sunsky_sequence_update): the same count, None keeps the
+        current values, the constructor's validation; a refused update leaves the sequence as it
+        was.  Afterwards frame() and eval() are bit for bit those of a new sequence with these
+        values.  Host-synchronous; drops the sampling distribution (call prepare_sampling again)
+        and restages the gradient records if prepare_grad was called."""
+        k = len(self)
+        d = None
+        if sun_directions is not None:
+            d = self._dirs(sun_directions)
+            if d.shape[0] != k:
+                raise ValueError(f"sun_directions must have shape ({k}, 3): update keeps the frame count")
+            d = _fa(d.reshape(-1).tolist())
+        check(lib().sunsky_sequence_update(self._h, d, self._per_frame(turbidity, k, "turbidity"),
+                                           self._per_frame(weights, k, "weights")))
+
+    def prepare_grad(self):
+        """Stages the per-frame gradient records and allocates eval_vjp's workspace
+        (sunsky_sequence_prepare_grad).  Host-synchronous; works on host-only sequences."""
+        check(lib().sunsky_sequence_prepare_grad(self._h))
+        self.grad_prepared = True
+
+    def frame_tangent(self, k):
+        """Frame k's gradient record: "dsky_turbidity" and "dsky_elevation" (nch, 10) d{A..I, rad}
+        along T and along a unit sun elevation, "dsun_local" (3, 3) [a] = d local sun / d s[a] and
+        "deta" (3,) d elevation / d s[a] for world axis a (normalisation and to_world folded in)."""
+        nch = self.info()["nb_channels"]
+        dt, de = (C.c_float * (nch * 10))(), (C.c_float * (nch * 10))()
+        dl, deta = (C.c_float * 9)(), (C.c_float * 3)()
+        check(lib().sunsky_sequence_get_frame_tangent(self._h, int(k), dt, de, dl, deta))
+        return {"dsky_turbidity": np.array(dt, dtype=np.float32).reshape(nch, 10),
+                "dsky_elevation": np.array(de, dtype=np.float32).reshape(nch, 10),
+                "dsun_local": np.array(dl, dtype=np.float32).reshape(3, 3), "deta": np.array(deta, dtype=np.float32)}
+
+    def eval_vjp(self, si_or_wi, d_out, wavelengths=None, active=None, grad=None):
+        """Reverse mode of eval(): with L = sum(d_out * eval(si)), accumulates dL/dw_k, dL/dT_k and
+        dL/ds_k (world space) into {"weights": (K,), "turbidity": (K,), "sun_directions": (K, 3)}
+        device tensors -- those of `grad` (an entry set to None is not computed) or new zeros --
+        and returns the dict.  Needs prepare_grad.  Reference-precision arithmetic, deterministic;
+        calls on one sequence share a workspace, so order them when they come from several streams."""
+        if self.device is None:
+            self.frame_tangent(0)   # an unprepared sequence says so first
+            raise ValueError("host-only sequence (over a host-only emitter) cannot launch kernels")
+        wi = getattr(si_or_wi, "wi", si_or_wi)
+        wi, vin = SunskyEmitter._vec_in(self, wi)
+        n = wi.shape[1]
+        k, lam_p, m = self._lambda(wavelengths, "sequence eval_vjp")
+        mask = SunskyEmitter._mask(self, active, n)
+        if d_out is None:
+            d_ptr, stride = None, n
+        else:
+            d_out = self._f32(d_out)
+            if tuple(d_out.shape) != (k, n):
+                raise ValueError(f"d_out must have shape ({k}, {n})")
+            d_ptr, stride = _ptr(d_out), d_out.stride(0)
+        count = len(self)
+        shapes = {"weights": (count,), "turbidity": (count,), "sun_directions": (count, 3)}
+        if grad is None:
+            grad = {key: torch.zeros(shape, dtype=torch.float32, device=self.device) for key, shape in shapes.items()}
+        ptrs = []
+        for key, shape in shapes.items():
+            g = grad.get(key)
+            if g is not None and (not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or g.device != self.device
+                                  or tuple(g.shape) != shape or not g.is_contiguous()):
+                raise ValueError(f"grad['{key}'] must be a contiguous float32 tensor of shape {shape} on {self.device}")
+            ptrs.append(_ptr(g))
+        check(lib().sunsky_sequence_eval_vjp(self._h, vin, lam_p, m, _ptr(mask), n, d_ptr, stride, *ptrs, self._stream()))
+        return grad
 
     # SunskyEmitter's tensor helpers read only self.device
     _f32 = SunskyEmitter._f32

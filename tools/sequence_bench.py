@@ -9,7 +9,10 @@ time.perf_counter around stream-synchronised bursts, warm, median of 5.  Prints 
 per K: both times, their ratio, and the sequence kernel's frame-evals/s (n K / t: a frame-eval
 does an eval's transcendental work with no HBM traffic).  Not part of bench.py.
   --sampling -- instead: sample_direction and pdf_direction of the prepared sequence beside
-                sequence.eval at the sampled directions (see sampling())."""
+                sequence.eval at the sampled directions (see sampling()).
+  --grad     -- instead: sequence.eval_vjp beside sequence.eval in reference precision and the
+                per-frame loop it replaces (see grad(); --no-loop leaves the loop out, for a
+                profiler run of the sequence kernels alone)."""
 import json
 import os
 import statistics
@@ -81,13 +84,95 @@ def sampling(ks, dev):
     print("sequence_bench sampling done")
 
 
+def grad(ks, dev, with_loop):
+    """--grad: the reverse-mode gradient of a K-frame sequence (weights, turbidities, sun
+    directions: 5 K values) for a normal cotangent, against two yardsticks of the same session:
+    sequence.eval in reference precision at the same n and K (the gradient runs reference
+    arithmetic), and the loop a user writes without it, K x (set sun_direction and turbidity,
+    parameters_changed, eval_vjp for dT and ds, eval + a dot product for dw) on one stream."""
+    g = torch.Generator(device=dev).manual_seed(3)
+    v = torch.randn((3, N), device=dev, generator=g)
+    v[2] = v[2].abs()
+    wi = -(v / v.norm(dim=0, keepdim=True)).contiguous()
+    si = ss.SurfaceInteraction3f(wi=wi)
+    d_out = torch.randn((3, N), device=dev, generator=g)
+    base = {"type": "sunsky", "sun_direction": [0.3, 0.4, 0.866], "turbidity": 3.0, "albedo": 0.2}
+    for k in ks:
+        dirs, turb, wts = frames(k)
+        seq = ss.SunskySequence(ss.load_dict(dict(base)), dirs, turb, wts)
+        seq.set_precision("reference")
+        t0 = time.perf_counter()
+        seq.prepare_grad()
+        t_prep = (time.perf_counter() - t0) * 1e3
+        out = torch.empty((3, N), device=dev)
+        gr = {"weights": torch.zeros(k, device=dev), "turbidity": torch.zeros(k, device=dev),
+              "sun_directions": torch.zeros((k, 3), device=dev)}
+        t_eval, all_eval = median_ms(lambda: seq.eval(wi, out=out))
+        t_vjp, all_vjp = median_ms(lambda: seq.eval_vjp(wi, d_out, grad=gr))
+        line = {"K": k, "n": N, "prepare_grad_ms": round(t_prep, 3), "eval_reference_ms": round(t_eval, 3),
+                "eval_vjp_ms": round(t_vjp, 3), "vjp_over_eval": round(t_vjp / t_eval, 3),
+                "frame_grads_per_s": round(N * k / (t_vjp * 1e-3), 0),
+                "eval_reference_ms_all": [round(t, 3) for t in all_eval], "eval_vjp_ms_all": [round(t, 3) for t in all_vjp]}
+        if with_loop:
+            em = ss.load_dict(dict(base))
+            em.set_precision("reference")
+            params = em.traverse()
+            gw = torch.zeros(k, device=dev)
+            g16 = torch.zeros((k, 16), device=dev)
+
+            def loop():
+                g16.zero_()
+                for i in range(k):
+                    params["sun_direction"] = dirs[i]
+                    params["turbidity"] = float(turb[i])
+                    params.update()
+                    em.eval_vjp(si, d_out, grad=g16[i])
+                    gw[i] = (em.eval(si) * d_out).sum()
+
+            t_loop, all_loop = median_ms(loop)
+            # Agreement of the two paths, away from the discs: set_param stages a sun direction as
+            # given while a sequence normalises it, so a few disc-edge lanes sit on different sides
+            # of the fp32 disc test (see main()), and a disc lane is ~1e5 x a sky lane in these
+            # signed sums.  Lanes within two half apertures of any frame's sun are masked out of
+            # both paths for this comparison only (the timings above are unmasked).  The loop's dT
+            # is per unit weight.
+            cut = float(np.cos(2.0 * em.info()["sun_half_aperture"]))
+            keep = torch.ones(N, dtype=torch.bool, device=dev)
+            for i in range(k):
+                s = torch.from_numpy(dirs[i] / np.linalg.norm(dirs[i])).to(dev)
+                keep &= (-(s[:, None] * wi).sum(0)) < cut
+            mask = keep.to(torch.uint8)
+            for key in gr:
+                gr[key].zero_()
+            seq.eval_vjp(wi, d_out, active=mask, grad=gr)
+            g16.zero_()
+            for i in range(k):
+                params["sun_direction"] = dirs[i]
+                params["turbidity"] = float(turb[i])
+                params.update()
+                em.eval_vjp(si, d_out, active=mask, grad=g16[i])
+                gw[i] = (em.eval(si, mask) * d_out).sum()
+            w_t = torch.from_numpy(wts).to(dev)
+            scale = lambda a: a.abs().max().clamp_min(1e-30)  # noqa: E731
+            line.update({"loop_ms": round(t_loop, 3), "speedup": round(t_loop / t_vjp, 2),
+                         "loop_ms_all": [round(t, 3) for t in all_loop],
+                         "lanes_compared": int(keep.sum().item()),
+                         "max_diff_weights": float(((gr["weights"] - gw).abs() / scale(gw)).max()),
+                         "max_diff_turbidity": float(((gr["turbidity"] - w_t * g16[:, 0]).abs() / scale(w_t * g16[:, 0])).max())})
+        print(json.dumps(line), flush=True)
+    print("sequence_bench grad done")
+
+
 def main():
-    args = [a for a in sys.argv[1:] if a != "--sampling"]
+    flags = ("--sampling", "--grad", "--no-loop")
+    args = [a for a in sys.argv[1:] if a not in flags]
     ks = [int(a) for a in args] or [24, 365]
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     if "--sampling" in sys.argv[1:]:
         return sampling(ks, dev)
+    if "--grad" in sys.argv[1:]:
+        return grad(ks, dev, "--no-loop" not in sys.argv[1:])
     g = torch.Generator(device=dev).manual_seed(3)
     v = torch.randn((3, N), device=dev, generator=g)
     v[2] = v[2].abs()
