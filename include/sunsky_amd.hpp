@@ -450,6 +450,29 @@ public:
                        void* stream = nullptr) const {
         check(sunsky_sequence_pdf_direction(s_, sunsky_vec3_in{ds.d.x, ds.d.y, ds.d.z}, active, n, pdf, stream));
     }
+    // Irradiance on oriented receivers (sunsky_amd.h): build the tables once (RGB: no wavelengths;
+    // spectral: the planes' wavelength list), then E_p(n) per receiver normal, planes as eval's
+    void prepare_irradiance(int n_z = 64, int n_phi = 256, const std::vector<float>& wavelengths = {}) {
+        check(sunsky_sequence_prepare_irradiance(s_, n_z, n_phi, wavelengths.empty() ? nullptr : wavelengths.data(),
+                                                 (int)wavelengths.size()));
+    }
+    sunsky_sequence_irradiance_desc irradiance_info() const {
+        sunsky_sequence_irradiance_desc d;
+        check(sunsky_sequence_irradiance_info(s_, &d));
+        return d;
+    }
+    std::vector<float> irradiance_table(sunsky_sequence_irradiance_table_id id) const {
+        size_t count = 0;
+        check(sunsky_sequence_get_irradiance_table(s_, (int)id, nullptr, 0, &count));
+        std::vector<float> t(count);
+        check(sunsky_sequence_get_irradiance_table(s_, (int)id, t.data(), count, &count));
+        return t;
+    }
+    void irradiance(Vector3 normal, size_t n, SpectrumOut out, const uint8_t* active = nullptr,
+                    void* stream = nullptr) const {
+        check(sunsky_sequence_irradiance(s_, sunsky_vec3_in{normal.x, normal.y, normal.z}, active, n, out.data,
+                                         out.stride ? out.stride : n, stream));
+    }
     // Per-frame gradients of the weighted sum (sunsky_amd.h).  update: empty = keep the current
     // values; the frame count does not change.
     struct FrameTangent {

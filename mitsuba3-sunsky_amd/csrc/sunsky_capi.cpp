@@ -168,6 +168,8 @@ void check_xform_form(hipModule_t mod, const std::string& path, bool want_identi
     X(SEQUENCE_PDF, "sunsky_sequence_pdf", 64, false, 1)                                           \
     X(SEQUENCE_EVAL_VJP_RGB, "sunsky_sequence_eval_vjp_rgb", kSeqGradBlocksPerCu, false, 1)        \
     X(SEQUENCE_EVAL_VJP_SPEC, "sunsky_sequence_eval_vjp_spec", kSeqGradBlocksPerCu, false, 1)      \
+    X(SEQUENCE_IRRADIANCE_RGB, "sunsky_sequence_irradiance_rgb", 64, false, 2)                     \
+    X(SEQUENCE_IRRADIANCE_SPEC, "sunsky_sequence_irradiance_spec", 64, false, 2)                   \
     X(DEBUG_SUN_SEGMENTS, "sunsky_debug_sun_segments", 16, false, 1)
 
 #define X(id, name, wg, dir, per) K_##id,
@@ -199,6 +201,7 @@ struct DeviceModule {
     hipFunction_t stage_sequence = nullptr;                                     // sequence_create
     hipFunction_t sequence_table = nullptr, sequence_suns = nullptr;            // sequence_prepare_sampling
     hipFunction_t stage_sequence_grad = nullptr, sequence_grad_reduce = nullptr;   // sequence_prepare_grad / _eval_vjp
+    hipFunction_t irradiance_table = nullptr, irradiance_flux = nullptr;        // sequence_prepare_irradiance
     int cu_count = 256;
 };
 
@@ -244,6 +247,8 @@ DeviceModule* module_for_device(int dev) {
     get(&m->sequence_suns, m->module, "sunsky_sequence_suns");
     get(&m->stage_sequence_grad, m->module, "sunsky_stage_sequence_grad");
     get(&m->sequence_grad_reduce, m->module, "sunsky_sequence_grad_reduce");
+    get(&m->irradiance_table, m->module, "sunsky_sequence_irradiance_table");
+    get(&m->irradiance_flux, m->module, "sunsky_sequence_irradiance_flux");
     get(&m->stage_radiance, m->module, "sunsky_stage_radiance");
     get(&m->quad_points, m->module, "sunsky_stage_quad_points");
     get(&m->quad_finish, m->module, "sunsky_stage_quad_finish");
@@ -688,6 +693,13 @@ struct sunsky_sequence {
     TangentStage* d_grad_stages = nullptr;
     float* d_grad_rows = nullptr;
     unsigned grad_max_grid = 0;
+    // irradiance (prepare_irradiance): the tables as read back (R_p and F_k[p], unweighted) and
+    // the staged device image the hot path walks (cell records, then sun records)
+    int irr_nz = 0, irr_nphi = 0, irr_planes = 0;   // 0: not prepared
+    float irr_omega = 0.f;
+    std::vector<float> irr_sky, irr_flux;
+    float* d_irr = nullptr;
+    SeqIrradiance irr = {};
 
     void require_device() const {
         if (!mod) throw std::invalid_argument("host-only sequence (over a sunsky_emitter_create_host emitter) cannot launch kernels");
@@ -700,6 +712,11 @@ struct sunsky_sequence {
         if (!samp_nz)
             throw std::invalid_argument("the sequence has no sampling distribution yet: call "
                                         "sunsky_sequence_prepare_sampling first");
+    }
+    void require_irradiance() const {
+        if (!irr_nz)
+            throw std::invalid_argument("the sequence has no irradiance tables yet: call "
+                                        "sunsky_sequence_prepare_irradiance first");
     }
     // The snapshot never changes, so an identity to_world takes the identity code object under
     // capture too (SUNSKY_AMD_GENERAL_XFORM=1: the general one always)
@@ -715,7 +732,7 @@ struct sunsky_sequence {
         if (hipGetDevice(&cur) == hipSuccess && cur != device) (void)hipSetDevice(device);
         (void)hipDeviceSynchronize();   // launches in flight may still read the records
         for (void* p : {(void*)d_state, d_frames, (void*)d_sun_rad, (void*)d_sun_ld, (void*)d_bake, (void*)d_samp,
-                        (void*)d_sky_ds, d_grads, (void*)d_grad_stages, (void*)d_grad_rows})
+                        (void*)d_sky_ds, d_grads, (void*)d_grad_stages, (void*)d_grad_rows, (void*)d_irr})
             if (p) (void)hipFree(p);
         if (bake_done) (void)hipEventDestroy(bake_done);
         if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
@@ -1045,6 +1062,128 @@ void seq_sampling_finish(sunsky_sequence* q, int nz, int nphi, std::vector<float
     s.sun_coef = (1.f - w_sky) * q->kargs.sun_pdf;
     s.dphi = kTwoPi / (float)nphi;
     s.inv_dphi = (float)nphi / kTwoPi;
+}
+
+// ---- irradiance tables (sunsky_sequence_prepare_irradiance)
+// sunsky_sequence_irradiance_table / _flux on the host (host-only sequences): the same
+// definitions through the SS_HD functions, with the host's libm.  sky: [planes][nz][nphi],
+// flux: [planes][count].
+void seq_irradiance_host(const sunsky_sequence* q, int nz, int nphi, const LambdaSet& L, int planes, float s2,
+                         std::vector<float>& sky_out, std::vector<float>& flux) {
+    const SunskyKArgs& K = q->kargs;
+    const bool rgb = q->variant == kRGB;
+    const float cie = (float)kCieYNormalization;
+    const size_t cells = (size_t)nz * (size_t)nphi;
+    for (int i = 0; i < nz; ++i)
+        for (int j = 0; j < nphi; ++j) {
+            const float3_ wo = seq_cell_centre(nz, nphi, i, j);
+            float acc[kSeqIrrMaxPlanes] = {0};
+            for (int k = 0; k < q->count; ++k) {
+                const SeqFrame<1>* h = seq_header(q, k);
+                const SkyChannel* sky = seq_sky(q, k);
+                const float gamma = unit_angle(mk3(h->sun_n[0], h->sun_n[1], h->sun_n[2]), wo);
+                if (rgb) {
+                    for (int c = 0; c < 3; ++c)
+                        acc[c] = fmaf(h->weight, K.sky_scale * render_sky(sky[c], wo.z, gamma) * cie, acc[c]);
+                    continue;
+                }
+                for (int p = 0; p < planes; ++p) {
+                    const int lo = L.lo[p], hi = lo + 1 < kNbWavelengths ? lo + 1 : lo;
+                    const float f = L.f[p];
+                    if (!(f >= 0.f)) continue;
+                    float v = K.sky_scale * render_sky(sky[lo], wo.z, gamma);
+                    if (f != 0.f) v = lerpf_(v, K.sky_scale * render_sky(sky[hi], wo.z, gamma), f);
+                    acc[p] = fmaf(h->weight, v, acc[p]);
+                }
+            }
+            for (int p = 0; p < planes; ++p) sky_out[(size_t)p * cells + (size_t)i * nphi + j] = acc[p];
+        }
+    const float* ds = q->h_sun_rad.data();
+    const float ring = kTwoPi / (float)kSeqFluxNphi;
+    constexpr int kPoints = kSeqFluxNu * kSeqFluxNphi;
+    std::vector<float> term((size_t)planes * kPoints);
+    for (int k = 0; k < q->count; ++k) {
+        const SeqFrame<1>* h = seq_header(q, k);
+        const float3_ sn = mk3(h->sun_n[0], h->sun_n[1], h->sun_n[2]);
+        const RadianceStage rs = {0.f, h->t_rem, h->t_low, h->t_high, 1};
+        float3_ fs, ft;
+        coordinate_system(sn, &fs, &ft);
+        std::fill(term.begin(), term.end(), 0.f);
+        for (int lane = 0; lane < kPoints; ++lane) {
+            const SeqFluxPoint pt = seq_flux_point(s2, lane / kSeqFluxNphi, lane % kSeqFluxNphi);
+            const float3_ d = frame_to_world(fs, ft, sn, mk3(pt.x, pt.y, pt.z));
+            if (!(sn.z >= 0.f && d.z >= 0.f)) continue;
+            const float ct = std::fmin(d.z, 1.f);
+            int pos = 0;
+            for (int j = 1; j < kNbSunSegments; ++j) pos += ct >= K.sun_seg_z[j] ? 1 : 0;
+            const float frac = (float)pos / (float)kNbSunSegments;
+            const float xs = (kHalfPi - acosf(ct)) - kHalfPi * (frac * frac * frac);
+            if (rgb) {
+                constexpr int per_c = kNbSunCtrlPts * kNbSunLdParams;
+                for (int c = 0; c < 3; ++c) {
+                    float s[per_c];
+                    for (int e = 0; e < per_c; ++e) s[e] = sun_param(ds, q->sun_block, pos * (3 * per_c) + c * per_c + e, rs);
+                    const float v = K.sun_scale * render_sun_rgb(s, 0, 0, xs, pt.u) * K.area_ratio * (float)kSpecToRgbSunConv;
+                    term[(size_t)c * kPoints + lane] = pt.W * (v * cie);
+                }
+                continue;
+            }
+            for (int p = 0; p < planes; ++p) {
+                const int lo = L.lo[p], hi = lo + 1;
+                const float f = L.f[p];
+                if (!(f >= 0.f)) continue;
+                auto poly = [&](int c) {
+                    float res = 0.f;
+                    for (int e = 0; e < kNbSunCtrlPts; ++e)
+                        res += powif_(xs, e) * sun_param(ds, q->sun_block, (pos * kNbWavelengths + c) * kNbSunCtrlPts + e, rs);
+                    return res;
+                };
+                float sun = poly(lo);
+                if (f != 0.f) sun = lerpf_(sun, hi < kNbWavelengths ? poly(hi) : 0.f, f);
+                const float ld = sun_limb_darkening(q->h_sun_ld.data(), lo, hi, f, pt.u);
+                term[(size_t)p * kPoints + lane] = pt.W * (K.sun_scale * sun * ld * K.area_ratio);
+            }
+        }
+        for (int p = 0; p < planes; ++p) {   // wave_sum's tree: lane l += lane l + off, off = 32 .. 1
+            float* t = &term[(size_t)p * kPoints];
+            for (int off = kPoints / 2; off > 0; off >>= 1)
+                for (int l = 0; l < off; ++l) t[l] += t[l + off];
+            flux[(size_t)p * q->count + k] = ring * t[0];
+        }
+    }
+}
+
+// The image the hot path walks, from the tables: per cell c_ij.xyz and omega R_p[i, j], then per
+// frame with a non-zero w_k F_k (order kept) s_k.xyz and w_k F_k[p]; records of seq_irr_record
+// floats.  Returns the number of sun records.
+int seq_irradiance_image(const sunsky_sequence* q, int nz, int nphi, int planes, float omega, const std::vector<float>& sky,
+                         const std::vector<float>& flux, std::vector<float>& image) {
+    const int rec = seq_irr_record(planes);
+    const size_t cells = (size_t)nz * (size_t)nphi;
+    image.assign((cells + (size_t)q->count) * rec, 0.f);
+    for (int i = 0; i < nz; ++i)
+        for (int j = 0; j < nphi; ++j) {
+            const size_t cell = (size_t)i * nphi + j;
+            const float3_ c = seq_cell_centre(nz, nphi, i, j);
+            float* r = &image[cell * rec];
+            r[0] = c.x; r[1] = c.y; r[2] = c.z;
+            for (int p = 0; p < planes; ++p) r[3 + p] = omega * sky[(size_t)p * cells + cell];
+        }
+    int nsuns = 0;
+    for (int k = 0; k < q->count; ++k) {
+        const SeqFrame<1>* h = seq_header(q, k);
+        float* r = &image[(cells + (size_t)nsuns) * rec];
+        bool any = false;
+        for (int p = 0; p < planes; ++p) {
+            r[3 + p] = h->weight * flux[(size_t)p * q->count + k];
+            any = any || r[3 + p] != 0.f;
+        }
+        if (!any) continue;
+        r[0] = h->sun_n[0]; r[1] = h->sun_n[1]; r[2] = h->sun_n[2];
+        ++nsuns;
+    }
+    image.resize((cells + (size_t)nsuns) * rec);
+    return nsuns;
 }
 
 }  // namespace
@@ -1857,6 +1996,7 @@ int sunsky_sequence_update(sunsky_sequence* seq, const float* sun_dirs, const fl
         seq->in_dirs = std::move(dirs); seq->in_turbidity = std::move(T); seq->in_weights = std::move(w);
         // the sampling distribution described the old frames
         seq->samp_nz = seq->samp_nphi = 0;
+        seq->irr_nz = seq->irr_nphi = seq->irr_planes = 0;   // and so did the irradiance tables
         if (seq->grad_ready) seq_stage_grad(seq);
     });
 }
@@ -2214,6 +2354,121 @@ int sunsky_sequence_pdf_direction(const sunsky_sequence* seq, sunsky_vec3_in d, 
         int count = seq->count;
         void* args[] = {&K, &S, &count, (void*)&d.x, (void*)&d.y, (void*)&d.z, &active, &n, &pdf};
         run_kernel(seq->mod, seq->xform_form(), seq->precision, K_SEQUENCE_PDF, n, args, (hipStream_t)stream);
+    });
+}
+
+int sunsky_sequence_prepare_irradiance(sunsky_sequence* seq, int n_z, int n_phi, const float* lam_host, int m) {
+    SUNSKY_PHASE("InitScene", "sequence_prepare_irradiance");
+    if (!seq) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sequence");
+    if (n_z < 1 || n_z > kSeqSampleMaxZ || n_phi < 4 || n_phi > kSeqSampleMaxPhi ||
+        (int64_t)n_z * n_phi > kSeqSampleMaxCells)
+        return fail(SUNSKY_ERROR_INVALID_VALUE,
+                    "irradiance table size out of range: 1 <= n_z <= 1024, 4 <= n_phi <= 4096, n_z * n_phi <= 2^20");
+    const bool spec = seq->variant == kSpectral;
+    if (spec && (!lam_host || m < 1 || m > kSeqIrrMaxPlanes))
+        return fail(SUNSKY_ERROR_INVALID_VALUE, "1..32 wavelengths required for the irradiance tables of a spectral sequence");
+    if (!spec && (lam_host || m)) return fail(SUNSKY_ERROR_INVALID_VALUE, "an RGB sequence takes no wavelengths");
+    const int planes = spec ? m : 3;
+    const size_t cells = (size_t)n_z * (size_t)n_phi;
+    if (cells * (size_t)planes > kSeqIrrMaxValues)
+        return fail(SUNSKY_ERROR_INVALID_VALUE, "irradiance table size out of range: n_z * n_phi * n_planes <= 2^22");
+    return guarded([&] {
+        const int count = seq->count;
+        SeqIrrTableArgs T;
+        std::memset(&T, 0, sizeof(T));
+        if (spec) T.L = make_lambda_set(lam_host, m);
+        T.nz = n_z;
+        T.nphi = n_phi;
+        T.planes = planes;
+        T.sin2_half_ap = 1.f / seq->kargs.inv_sin2_half_ap;
+        const float omega = (float)(2.0 * 3.14159265358979323846 / (double)cells);
+        std::vector<float> sky(cells * planes), flux((size_t)planes * count), image;
+        auto accept = [&] {
+            seq->irr_sky = std::move(sky);
+            seq->irr_flux = std::move(flux);
+            seq->irr_omega = omega;
+            seq->irr_nz = n_z;
+            seq->irr_nphi = n_phi;
+            seq->irr_planes = planes;
+        };
+        if (seq->device < 0) {
+            seq_irradiance_host(seq, n_z, n_phi, T.L, planes, T.sin2_half_ap, sky, flux);
+            accept();
+            return;
+        }
+        DeviceScope g(seq->device);
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");   // nothing may still read the old image
+        seq->irr_nz = seq->irr_nphi = seq->irr_planes = 0;
+        if (seq->d_irr) hip_check(hipFree(seq->d_irr), "hipFree");
+        seq->d_irr = nullptr;
+        // the image's allocation first holds the two tables the kernels write: a record has 3 floats
+        // more than planes, so it is never smaller
+        const size_t rec = (size_t)seq_irr_record(planes);
+        const size_t image_cap = (cells + (size_t)count) * rec;
+        hip_check(hipMalloc(&seq->d_irr, sizeof(float) * image_cap), "hipMalloc");
+        T.sky = seq->d_irr;
+        T.flux = seq->d_irr + sky.size();
+        const SunskyKArgs* K = seq->d_state;
+        SeqArgs A = seq->args();
+        void* args[] = {&K, &A, &T};
+        const unsigned grid = (unsigned)std::min<size_t>((cells + kBlock - 1) / kBlock, (size_t)seq->mod->cu_count * 64);
+        launch(seq->mod->irradiance_table, grid, nullptr, args);
+        hip_check(hipModuleLaunchKernel(seq->mod->irradiance_flux, (unsigned)std::min(count, 65535), 1, 1, 64, 1, 1, 0,
+                                        nullptr, args, nullptr), "hipModuleLaunchKernel(sunsky_sequence_irradiance_flux)");
+        hip_check(hipStreamSynchronize(nullptr), "hipStreamSynchronize");
+        hip_check(hipMemcpy(sky.data(), T.sky, sizeof(float) * sky.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+        hip_check(hipMemcpy(flux.data(), T.flux, sizeof(float) * flux.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+        const int nsuns = seq_irradiance_image(seq, n_z, n_phi, planes, omega, sky, flux, image);
+        hip_check(hipMemcpy(seq->d_irr, image.data(), sizeof(float) * image.size(), hipMemcpyHostToDevice), "hipMemcpy");
+        seq->irr = SeqIrradiance{seq->d_irr, seq->d_irr + cells * rec, n_z, n_phi, nsuns, planes};
+        accept();
+    });
+}
+
+int sunsky_sequence_irradiance_info(const sunsky_sequence* seq, sunsky_sequence_irradiance_desc* out) {
+    if (!seq || !out) return fail(SUNSKY_ERROR_INVALID_VALUE, "null argument");
+    return guarded([&] {
+        seq->require_irradiance();
+        out->n_z = seq->irr_nz;
+        out->n_phi = seq->irr_nphi;
+        out->n_planes = seq->irr_planes;
+        out->omega = seq->irr_omega;
+    });
+}
+
+int sunsky_sequence_get_irradiance_table(const sunsky_sequence* seq, int id, float* out, size_t cap, size_t* count) {
+    if (!seq) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sequence");
+    return guarded([&] {
+        seq->require_irradiance();
+        const std::vector<float>* t = nullptr;
+        switch (id) {
+            case SUNSKY_SEQUENCE_IRRADIANCE_TABLE_SKY: t = &seq->irr_sky; break;
+            case SUNSKY_SEQUENCE_IRRADIANCE_TABLE_SUN_FLUX: t = &seq->irr_flux; break;
+            default: throw std::invalid_argument("unknown sequence irradiance table id");
+        }
+        if (count) *count = t->size();
+        if (out) std::memcpy(out, t->data(), sizeof(float) * std::min(cap, t->size()));
+    });
+}
+
+int sunsky_sequence_irradiance(const sunsky_sequence* seq, sunsky_vec3_in nrm, const uint8_t* active, size_t n,
+                               float* out, size_t ostride, void* stream) {
+    SUNSKY_PHASE("EndpointEvaluate", "sequence_irradiance");
+    if (!seq) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sequence");
+    if (n == 0) return SUNSKY_OK;
+    if (!nrm.x || !nrm.y || !nrm.z || !out) return fail(SUNSKY_ERROR_INVALID_VALUE, "null normal / output pointer");
+    if (n > 0xffffffffull) return fail(SUNSKY_ERROR_INVALID_VALUE, "more than 2^32 receivers");
+    return guarded([&] {
+        seq->require_irradiance();   // first: the message names the missing call on any sequence
+        seq->require_device();
+        if (seq->irr_planes > 1 && ostride < n) throw std::invalid_argument("out_stride < n");
+        DeviceScope g(seq->device);
+        const SunskyKArgs* K = seq->d_state;
+        SeqIrradiance S = seq->irr;
+        void* args[] = {&K, &S, (void*)&nrm.x, (void*)&nrm.y, (void*)&nrm.z, &active, &n, &out, &ostride};
+        run_kernel(seq->mod, seq->xform_form(), seq->precision,
+                   seq->variant == kSpectral ? K_SEQUENCE_IRRADIANCE_SPEC : K_SEQUENCE_IRRADIANCE_RGB, n, args,
+                   (hipStream_t)stream);
     });
 }
 

@@ -213,4 +213,61 @@ struct SeqTableArgs {
 };
 static_assert(sizeof(SeqTableArgs) == 16 + 4 * kNbWavelengths + 12, "SeqTableArgs layout");
 
+// ---------------------------------------------------------------- sequence irradiance
+// sunsky_sequence_prepare_irradiance / sunsky_sequence_irradiance (sunsky_amd.h has the
+// definition).  The sun flux F_k is a 4 x 16 rule over frame k's cone: 4 Gauss-Legendre nodes
+// in u = cos psi on [0, 1] (kSeqFluxU, kSeqFluxG), 16 midpoints in azimuth; one lane per point.
+constexpr int kSeqFluxNu = 4, kSeqFluxNphi = 16;
+static_assert(kSeqFluxNu * kSeqFluxNphi == 64, "one wave per frame, one lane per point of the rule");
+constexpr double kSeqFluxU[kSeqFluxNu] = {0.06943184420297371, 0.33000947820757187, 0.66999052179242813,
+                                          0.93056815579702629};
+constexpr double kSeqFluxG[kSeqFluxNu] = {0.17392742256872693, 0.32607257743127307, 0.32607257743127307,
+                                          0.17392742256872693};
+constexpr int kSeqIrrMaxPlanes = kMaxBroadcastLambda;
+constexpr size_t kSeqIrrMaxValues = (size_t)1 << 22;   // n_z n_phi n_planes
+
+// Floats of one record of the staged image: a direction (cell centre c_ij or sun s_k), then the
+// n_planes weighted values (omega R_p[i, j] or w_k F_k[p]), padded to 16 bytes.  8 for RGB.
+constexpr int seq_irr_record(int planes) { return (3 + planes + 3) & ~3; }
+static_assert(seq_irr_record(3) == 8 && seq_irr_record(1) == 4 && seq_irr_record(kSeqIrrMaxPlanes) == 36, "record size");
+
+// Point (a, b) of the flux rule for a cone of sin^2(half aperture) = s2: the direction in the
+// sun's frame (sin gamma cos phi, sin gamma sin phi, cos gamma) and the ring weight
+// W_a = g_a u_a s2 / cos gamma_a (sum_a W_a 2 pi = the cone's solid angle).
+struct SeqFluxPoint { float x, y, z, u, W; };
+SS_HD inline SeqFluxPoint seq_flux_point(float s2, int a, int b) {
+    SS_NO_CONTRACT
+    SeqFluxPoint p;
+    p.u = (float)kSeqFluxU[a];
+    const float sin2 = (1.f - p.u * p.u) * s2;
+    p.z = sqrtf(1.f - sin2);
+    const float sg = sqrtf(sin2);
+    const float phi = ((float)b + 0.5f) * (kTwoPi / (float)kSeqFluxNphi);
+    p.x = sg * cosf(phi);
+    p.y = sg * sinf(phi);
+    p.W = (float)kSeqFluxG[a] * p.u * s2 / p.z;
+    return p;
+}
+
+// sunsky_sequence_irradiance_table / sunsky_sequence_irradiance_flux (prepare_irradiance): one
+// lane per cell, one wave per frame.  L: the spectral wavelength list (m = n_planes), unused for RGB.
+struct SeqIrrTableArgs {
+    float* sky;                // [planes][nz][nphi] R_p, written
+    float* flux;               // [planes][count] F_k[p], written
+    LambdaSet L;
+    int nz, nphi, planes;
+    float sin2_half_ap;        // sin^2(half aperture) = 1 / SunskyKArgs::inv_sin2_half_ap
+};
+static_assert(sizeof(SeqIrrTableArgs) == 16 + sizeof(LambdaSet) + 4 + 16 && offsetof(SeqIrrTableArgs, nz) == 16 + sizeof(LambdaSet),
+              "SeqIrrTableArgs layout");
+
+// The hot path's view: the staged image.  Every record is 16-byte aligned and read with one
+// address per wave.
+struct SeqIrradiance {
+    const float* cells;        // [ncells] records: c_ij.xyz, omega R_p[i, j]
+    const float* suns;         // [nsuns] records: s_k.xyz, w_k F_k[p] (frames with a zero flux left out, order kept)
+    int nz, nphi, nsuns, planes;
+};
+static_assert(sizeof(SeqIrradiance) == 32 && offsetof(SeqIrradiance, nz) == 16, "SeqIrradiance layout");
+
 }  // namespace sunsky

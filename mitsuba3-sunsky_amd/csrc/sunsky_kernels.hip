@@ -24,6 +24,8 @@
 //    order with full-precision libm.  Both are parity-tested against the oracle.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "sunsky_kernel_args.h"
 #include "sunsky_math.h"
 #include "sunsky_staging.h"
@@ -4607,6 +4609,41 @@ __device__ __forceinline__ int seq_segment_ref(const SunskyKArgs& K, float cos_t
     return pos;
 }
 
+// The reference-precision disc term from its coordinates (segment pos, elevation xs within it,
+// cos psi): what seq_disc_rgb<false> / seq_disc_spec<false> add for a direction, and what the
+// irradiance flux rule evaluates at its nodes with cos psi given (sunsky_sequence_irradiance_flux)
+__device__ __forceinline__ void seq_disc_rgb_at(const SunskyKArgs& Kf, const float* ds, int block, const RadianceStage& rs,
+                                                int pos, float xs, float cpsi, float v[3]) {
+    constexpr int per_c = kNbSunCtrlPts * kNbSunLdParams;
+    const float conv = (float)kSpecToRgbSunConv;
+#pragma unroll 1
+    for (int c = 0; c < 3; ++c) {
+        float s[per_c];
+#pragma unroll
+        for (int e = 0; e < per_c; ++e) s[e] = sun_param(ds, block, pos * (3 * per_c) + c * per_c + e, rs);
+        v[c] += Kf.sun_scale * render_sun_rgb(s, 0, 0, xs, cpsi) * Kf.area_ratio * conv;
+    }
+}
+
+// sun_spec_term<false>: render_sun_spec x sun_limb_darkening for the channel pair (lo, lo + 1, f)
+__device__ __forceinline__ float seq_disc_spec_at(const SunskyKArgs& Kf, const float* ds, int block,
+                                                  const RadianceStage& rs, int pos, float xs, float cpsi, int lo, float f,
+                                                  float o) {
+    const int hi = lo + 1;
+    auto poly = [&](int c) {
+        const int q = (pos * kNbWavelengths + c) * kNbSunCtrlPts;
+        float res = 0.f;
+#pragma unroll
+        for (int e = 0; e < kNbSunCtrlPts; ++e) res += powif_(xs, e) * sun_param(ds, block, q + e, rs);
+        return res;
+    };
+    const float sa = poly(lo);
+    float sun = sa;
+    if (f != 0.f) sun = lerpf_(sa, hi < kNbWavelengths ? poly(hi) : 0.f, f);
+    const float ld = sun_limb_darkening(Kf.sun_ld, lo, hi, f, cpsi);
+    return o + Kf.sun_scale * sun * ld * Kf.area_ratio;
+}
+
 // RGB disc term of frame k added to the lane's 3 sky values (the rare branch)
 template <bool FAST>
 __device__ __forceinline__ void seq_disc_rgb(const SunskyKArgs& K, const SeqArgs& A, int k, const DirTerms& t,
@@ -4636,15 +4673,7 @@ __device__ __forceinline__ void seq_disc_rgb(const SunskyKArgs& K, const SeqArgs
     } else {
         float xs;
         const int pos = seq_segment_ref(Kf, t.cos_theta, &xs);
-        const float cpsi = cos_psi(t.gamma, Kf.inv_sin2_half_ap);
-        const float conv = (float)kSpecToRgbSunConv;
-#pragma unroll 1
-        for (int c = 0; c < 3; ++c) {
-            float s[per_c];
-#pragma unroll
-            for (int e = 0; e < per_c; ++e) s[e] = sun_param(ds, block, pos * (3 * per_c) + c * per_c + e, rs);
-            v[c] += Kf.sun_scale * render_sun_rgb(s, 0, 0, xs, cpsi) * Kf.area_ratio * conv;
-        }
+        seq_disc_rgb_at(Kf, ds, block, rs, pos, xs, cos_psi(t.gamma, Kf.inv_sin2_half_ap), v);
     }
 }
 
@@ -4676,22 +4705,10 @@ __device__ __forceinline__ float seq_disc_spec(const SunskyKArgs& K, const SeqAr
             ld = fma(ld, d.cpsi, coef);
         }
         return (float)fma((double)Kf.sun_mul, sun * ld, (double)o);
-    } else {   // sun_spec_term<false>: render_sun_spec x sun_limb_darkening
+    } else {
         float xs;
         const int pos = seq_segment_ref(Kf, t.cos_theta, &xs);
-        const float cpsi = cos_psi(t.gamma, Kf.inv_sin2_half_ap);
-        auto poly = [&](int c) {
-            const int q = (pos * kNbWavelengths + c) * kNbSunCtrlPts;
-            float res = 0.f;
-#pragma unroll
-            for (int e = 0; e < kNbSunCtrlPts; ++e) res += powif_(xs, e) * sun_param(ds, block, q + e, rs);
-            return res;
-        };
-        const float sa = poly(lo);
-        float sun = sa;
-        if (f != 0.f) sun = lerpf_(sa, hi < kNbWavelengths ? poly(hi) : 0.f, f);
-        const float ld = sun_limb_darkening(Kf.sun_ld, lo, hi, f, cpsi);
-        return o + Kf.sun_scale * sun * ld * Kf.area_ratio;
+        return seq_disc_spec_at(Kf, ds, block, rs, pos, xs, cos_psi(t.gamma, Kf.inv_sin2_half_ap), lo, f, o);
     }
 }
 
@@ -5427,44 +5444,57 @@ SS_SEQUENCE_SAMPLING(_ref, false)
 // prepare_sampling's table: cell (i, j) = Y(sum_k w_k sky_k(centre)), the accumulate loop in
 // reference precision with the disc branch off, one cell per lane.  Y: the RGB luminance
 // weights, or sum_c cie_y[c] L_c / 11 over the 11 nodes (quad_finish's).
+// The frame loop of the sky tables (sunsky_sequence_table, sunsky_sequence_irradiance_table):
+// sum_k w_k sky_k(s) of the N channels c[], reference precision, the disc branch off, added in
+// frame order as fma(w_k, v, acc).  RGB = true: N = 3 planes, each x MI_CIE_Y_NORMALIZATION.
+// Otherwise one plane: channel c[0], or (N = 2) the lerp of c[0] and c[1] by f != 0, as
+// seq_spec_body forms a wavelength between two nodes.
+template <bool RGB, int N>
+__device__ __forceinline__ void seq_sky_sum(const SunskyKArgs& K, const SeqArgs& A, const SeqDir& s, const int (&c)[N],
+                                            float f, float (&acc)[RGB ? 3 : 1]) {
+    static_assert(RGB ? N == 3 : (N == 1 || N == 2), "3 RGB planes, or one plane from one or two nodes");
+    const int nch = RGB ? 3 : kNbWavelengths, count = A.count;
+    const float cie = (float)kCieYNormalization;
+#pragma unroll
+    for (int p = 0; p < (RGB ? 3 : 1); ++p) acc[p] = 0.f;
+    SeqHot<false, N> cur = seq_load<false, N>(A.frames, nch, 0, c);
+#pragma unroll 1
+    for (int k = 0; k < count; ++k) {
+        const SeqHot<false, N> nxt = seq_load<false, N>(A.frames, nch, k + 1 < count ? k + 1 : k, c);
+        const DirTerms t = seq_frame_terms<false>(s, cur.sn, K.cos_cutoff);
+        if constexpr (RGB) {
+#pragma unroll
+            for (int p = 0; p < 3; ++p) acc[p] = fmaf(cur.w, sky_eval<false>(cur.ch[p], t, K.sky_scale) * cie, acc[p]);
+        } else {
+            float v = sky_eval<false>(cur.ch[0], t, K.sky_scale);
+            if constexpr (N == 2)
+                if (f != 0.f) v = lerpf_(v, sky_eval<false>(cur.ch[1], t, K.sky_scale), f);
+            acc[0] = fmaf(cur.w, v, acc[0]);
+        }
+        cur = nxt;
+    }
+}
+
 extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_table(const SunskyKArgs* __restrict__ Kp,
                                                                              SeqArgs A, SeqTableArgs T) {
     const SunskyKArgs& K = *Kp;
     const size_t n = (size_t)T.nz * (size_t)T.nphi, stride = (size_t)gridDim.x * blockDim.x;
-    const int count = A.count;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const float3_ wo = seq_cell_centre(T.nz, T.nphi, (int)(i / (size_t)T.nphi), (int)(i % (size_t)T.nphi));
         const SeqDir s = seq_dir<false>(wo, true);
         float y = 0.f;
         if (K.variant == kRGB) {
             const int chans[3] = {0, 1, 2};
-            const float cie = (float)kCieYNormalization;
-            float acc[3] = {0.f, 0.f, 0.f};
-            SeqHot<false, 3> cur = seq_load<false, 3>(A.frames, 3, 0, chans);
-#pragma unroll 1
-            for (int k = 0; k < count; ++k) {
-                const SeqHot<false, 3> nxt = seq_load<false, 3>(A.frames, 3, k + 1 < count ? k + 1 : k, chans);
-                const DirTerms t = seq_frame_terms<false>(s, cur.sn, K.cos_cutoff);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) acc[c] = fmaf(cur.w, sky_eval<false>(cur.ch[c], t, K.sky_scale) * cie, acc[c]);
-                cur = nxt;
-            }
+            float acc[3];
+            seq_sky_sum<true, 3>(K, A, s, chans, 0.f, acc);
             y = luminance_rgb(acc);
         } else {
 #pragma unroll 1
             for (int c = 0; c < kNbWavelengths; ++c) {
                 const int chans[1] = {c};
-                float acc = 0.f;
-                SeqHot<false, 1> cur = seq_load<false, 1>(A.frames, kNbWavelengths, 0, chans);
-#pragma unroll 1
-                for (int k = 0; k < count; ++k) {
-                    const SeqHot<false, 1> nxt =
-                        seq_load<false, 1>(A.frames, kNbWavelengths, k + 1 < count ? k + 1 : k, chans);
-                    const DirTerms t = seq_frame_terms<false>(s, cur.sn, K.cos_cutoff);
-                    acc = fmaf(cur.w, sky_eval<false>(cur.ch[0], t, K.sky_scale), acc);
-                    cur = nxt;
-                }
-                y = fmaf(T.cie_y[c], acc, y);
+                float acc[1];
+                seq_sky_sum<false, 1>(K, A, s, chans, 0.f, acc);
+                y = fmaf(T.cie_y[c], acc[0], y);
             }
             y = y / (float)kNbWavelengths;
         }
@@ -5497,6 +5527,207 @@ extern "C" __global__ __launch_bounds__(64) void sunsky_sequence_suns(const Suns
         if (threadIdx.x == 0) T.B[k] = fmaxf(y, 0.f);
     }
 }
+
+// ======================================================================
+// Irradiance on oriented receivers (sunsky_sequence_prepare_irradiance / _irradiance; the
+// definition is in sunsky_amd.h):
+//   E_p(n) = sum_i sum_j omega R_p[i, j] max(0, n_l . c_ij) + sum_k w_k F_k[p] max(0, n_l . s_k)
+// prepare_irradiance runs the two table kernels below and stages one image of 16-byte aligned
+// records (direction, then the weighted plane values: seq_irr_record); the hot path is a
+// receiver x record contraction with one receiver per lane.
+// ======================================================================
+
+// R_p[i, j] = (sum_k w_k sky_k(c_ij))_p: sunsky_sequence_table's frame loop with the planes
+// kept.  One cell per lane; spectral: one pass per requested wavelength (an invalid one: 0).
+extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_irradiance_table(
+    const SunskyKArgs* __restrict__ Kp, SeqArgs A, SeqIrrTableArgs T) {
+    const SunskyKArgs& K = *Kp;
+    const size_t n = (size_t)T.nz * (size_t)T.nphi, stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const float3_ wo = seq_cell_centre(T.nz, T.nphi, (int)(i / (size_t)T.nphi), (int)(i % (size_t)T.nphi));
+        const SeqDir s = seq_dir<false>(wo, true);
+        if (K.variant == kRGB) {
+            const int chans[3] = {0, 1, 2};
+            float acc[3];
+            seq_sky_sum<true, 3>(K, A, s, chans, 0.f, acc);
+#pragma unroll
+            for (int p = 0; p < 3; ++p) T.sky[(size_t)p * n + i] = acc[p];
+        } else {
+#pragma unroll 1
+            for (int q = 0; q < T.planes; ++q) {
+                const int lo = T.L.lo[q];
+                const float f = T.L.f[q];
+                float acc[1] = {0.f};
+                if (f >= 0.f) {
+                    const int chans[2] = {lo, lo + 1 < kNbWavelengths ? lo + 1 : lo};
+                    seq_sky_sum<false, 2>(K, A, s, chans, f, acc);
+                }
+                T.sky[(size_t)q * n + i] = acc[0];
+            }
+        }
+    }
+}
+
+// F_k[p]: frame k's disc term alone integrated over its cone by the 4 x 16 rule
+// (seq_flux_point), reference precision.  One wave per frame, lane = point (a, b): the
+// direction through Frame(s_k), its cos theta and elevation segment as eval takes them, cos psi
+// = u_a as given (not recomputed from the rounded direction, no cone test); 0 below the horizon
+// and for a sun below it.  The 64 weighted values are added by wave_sum's fixed tree.
+extern "C" __global__ __launch_bounds__(64) void sunsky_sequence_irradiance_flux(const SunskyKArgs* __restrict__ Kp,
+                                                                                 SeqArgs A, SeqIrrTableArgs T) {
+    const SunskyKArgs& K = *Kp;
+    const int lane = threadIdx.x;
+    const SeqFluxPoint pt = seq_flux_point(T.sin2_half_ap, lane / kSeqFluxNphi, lane % kSeqFluxNphi);
+    const float ring = kTwoPi / (float)kSeqFluxNphi;
+    for (int k = blockIdx.x; k < A.count; k += gridDim.x) {
+        seq_cfloat_p rec = seq_record(A.frames, K.nch, k);
+        const float3_ sn = mk3(rec[0], rec[1], rec[2]);
+        const RadianceStage rs = seq_sun_stage(rec);
+        float3_ fs, ft;
+        coordinate_system(sn, &fs, &ft);
+        const float3_ d = frame_to_world(fs, ft, sn, mk3(pt.x, pt.y, pt.z));
+        const bool up = sn.z >= 0.f && d.z >= 0.f;
+        float xs = 0.f;
+        const int pos = up ? seq_segment_ref(K, fminf(d.z, 1.f), &xs) : 0;
+        if (K.variant == kRGB) {
+            float v[3] = {0.f, 0.f, 0.f};
+            if (up) seq_disc_rgb_at(K, A.sun_rad_ds, A.sun_block, rs, pos, xs, pt.u, v);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float sum = wave_sum(pt.W * (v[c] * (float)kCieYNormalization));
+                if (lane == 0) T.flux[(size_t)c * A.count + k] = ring * sum;
+            }
+        } else {
+#pragma unroll 1
+            for (int q = 0; q < T.planes; ++q) {
+                const int lo = T.L.lo[q];
+                const float f = T.L.f[q];
+                float v = 0.f;
+                if (up && f >= 0.f) v = seq_disc_spec_at(K, A.sun_rad_ds, A.sun_block, rs, pos, xs, pt.u, lo, f, 0.f);
+                const float sum = wave_sum(pt.W * v);
+                if (lane == 0) T.flux[(size_t)q * A.count + k] = ring * sum;
+            }
+        }
+    }
+}
+
+// Two receivers per lane: every operation of the contraction is one packed fp32 instruction
+// over the pair (the record's scalar broadcast to both halves), except the clamp.
+typedef float seq_f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ seq_f2 seq_fma2(seq_f2 a, float b, seq_f2 c) {
+    const seq_f2 bb = {b, b};
+    return __builtin_elementwise_fma(a, bb, c);
+}
+
+// One pass of the contraction for the NP planes [p0, p0 + NP) of a lane's two receivers with
+// local normals (nx, ny, nz)[0 / 1].  The records are read through the constant address space
+// with one address per wave (scalar loads into SGPRs, REC floats apart; REC = 0: `rec` at run
+// time), so a lane's work per record and receiver is the dot product, the clamp and NP FMAs.
+// The order is the contract: a row's cells in column order into a row sum that starts at 0,
+// the row sums in row order into the plane's sum, then the suns in list order, every
+// product-and-add one fma; the two receivers of a lane never meet.
+template <int NP, int REC>
+__device__ __forceinline__ void seq_irr_pass(const SeqIrradiance& S, int rec, int p0, seq_f2 nx, seq_f2 ny, seq_f2 nz,
+                                             seq_f2 (&acc)[NP]) {
+    if constexpr (REC != 0) rec = REC;
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wold-style-cast"
+    seq_cfloat_p r = (seq_cfloat_p)__builtin_assume_aligned(S.cells, 16) + 3 + p0;
+    seq_cfloat_p u = (seq_cfloat_p)__builtin_assume_aligned(S.suns, 16) + 3 + p0;
+#pragma clang diagnostic pop
+    const seq_f2 zero = {0.f, 0.f};
+    // max(0, n . d) for both receivers, d the direction in front of the plane values at q
+    auto cosine = [&](seq_cfloat_p q) {
+        const seq_f2 d = seq_fma2(nz, q[-1 - p0], seq_fma2(ny, q[-2 - p0], nx * q[-3 - p0]));
+        return __builtin_elementwise_max(d, zero);
+    };
+#pragma unroll
+    for (int p = 0; p < NP; ++p) acc[p] = zero;
+#pragma unroll 1
+    for (int i = 0; i < S.nz; ++i) {
+        seq_f2 row[NP];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) row[p] = zero;
+#pragma unroll 4
+        for (int j = 0; j < S.nphi; ++j, r += rec) {
+            const seq_f2 c = cosine(r);
+#pragma unroll
+            for (int p = 0; p < NP; ++p) row[p] = seq_fma2(c, r[p], row[p]);
+        }
+#pragma unroll
+        for (int p = 0; p < NP; ++p) acc[p] += row[p];
+    }
+#pragma unroll 1
+    for (int k = 0; k < S.nsuns; ++k, u += rec) {
+        const seq_f2 c = cosine(u);
+#pragma unroll
+        for (int p = 0; p < NP; ++p) acc[p] = seq_fma2(c, u[p], acc[p]);
+    }
+}
+
+// Two receivers per lane, t and t + ceil(n / 2) (both streams coalesced), grid-stride over the
+// pairs.  RGB: one pass of 3 planes over 32-byte records.  Spectral: passes of 8, 4, 2 and 1
+// planes (a plane's sum does not depend on the pass it is in).
+template <bool RGB>
+__device__ __forceinline__ void seq_irradiance_body(const SunskyKArgs& K, const SeqIrradiance& S, const float* nx,
+                                                    const float* ny, const float* nz, const uint8_t* active, size_t n,
+                                                    float* __restrict__ out, size_t ostride) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x, pairs = (n + 1) / 2;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < pairs; t += stride) {
+        const size_t idx[2] = {t, t + pairs};
+        const bool has[2] = {true, idx[1] < n};
+        bool m[2];
+        float3_ nl[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const size_t i = has[h] ? idx[h] : t;
+            m[h] = !active || active[i] != 0;
+            nl[h] = to_local(K, mk3(nx[i], ny[i], nz[i]));
+        }
+        const seq_f2 lx = {nl[0].x, nl[1].x}, ly = {nl[0].y, nl[1].y}, lz = {nl[0].z, nl[1].z};
+        auto store = [&](int p, seq_f2 v) {
+            store_nt(m[0] ? v[0] : 0.f, out + (size_t)p * ostride + idx[0]);
+            if (has[1]) store_nt(m[1] ? v[1] : 0.f, out + (size_t)p * ostride + idx[1]);
+        };
+        if constexpr (RGB) {
+            seq_f2 acc[3];
+            seq_irr_pass<3, seq_irr_record(3)>(S, 0, 0, lx, ly, lz, acc);
+#pragma unroll
+            for (int p = 0; p < 3; ++p) store(p, acc[p]);
+        } else {
+            const int rec = seq_irr_record(S.planes);
+            int p0 = 0;
+            auto pass = [&](auto np) {
+                constexpr int NP = decltype(np)::value;
+                seq_f2 acc[NP];
+                seq_irr_pass<NP, 0>(S, rec, p0, lx, ly, lz, acc);
+#pragma unroll
+                for (int p = 0; p < NP; ++p) store(p0 + p, acc[p]);
+                p0 += NP;
+            };
+#pragma unroll 1
+            while (S.planes - p0 >= 8) pass(std::integral_constant<int, 8>());
+            if (S.planes - p0 >= 4) pass(std::integral_constant<int, 4>());
+            if (S.planes - p0 >= 2) pass(std::integral_constant<int, 2>());
+            if (S.planes - p0 >= 1) pass(std::integral_constant<int, 1>());
+        }
+    }
+}
+
+// Both precisions' names run the same body: the tables are reference precision by definition
+#define SS_SEQUENCE_IRRADIANCE(SUFFIX)                                                                         \
+    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_irradiance_rgb##SUFFIX(             \
+        const SunskyKArgs* __restrict__ Kp, SeqIrradiance S, const float* nx, const float* ny, const float* nz, \
+        const uint8_t* active, size_t n, float* out, size_t ostride) {                                         \
+        seq_irradiance_body<true>(*Kp, S, nx, ny, nz, active, n, out, ostride);                                \
+    }                                                                                                          \
+    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_irradiance_spec##SUFFIX(            \
+        const SunskyKArgs* __restrict__ Kp, SeqIrradiance S, const float* nx, const float* ny, const float* nz, \
+        const uint8_t* active, size_t n, float* out, size_t ostride) {                                         \
+        seq_irradiance_body<false>(*Kp, S, nx, ny, nz, active, n, out, ostride);                               \
+    }
+SS_SEQUENCE_IRRADIANCE(_fast)
+SS_SEQUENCE_IRRADIANCE(_ref)
 
 // Batched staging of a sequence's records: workgroup = frame, sunsky_stage_radiance's sky part
 // (radiance_param per entry, then one thread per channel folds it) from the RadianceStage

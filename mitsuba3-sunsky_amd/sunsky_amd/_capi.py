@@ -62,6 +62,11 @@ class SequenceSamplingDesc(C.Structure):
                 ("sun_mass", C.c_float)]
 
 
+class SequenceIrradianceDesc(C.Structure):
+    _fields_ = [("n_z", C.c_int), ("n_phi", C.c_int), ("n_planes", C.c_int), ("omega", C.c_float)]
+
+
+SEQUENCE_IRRADIANCE_TABLES = {"sky": 0, "sun_flux": 1}
 SEQUENCE_TABLES = {"sky": 0, "row_cdf": 1, "cell_cdf": 2, "q": 3, "frame_cdf": 4, "B": 5}
 # sunsky_sequence_eval_vjp's launch shape (csrc/sunsky_kernel_args.h): workgroups per CU, the
 # workspace bound in floats, the frame count up to which a wave's row lives in LDS
@@ -128,6 +133,10 @@ _SIGS = {
     "sunsky_sequence_get_frame_tangent": (C.c_int, [vp, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p]),
     "sunsky_sequence_eval_vjp": (C.c_int, [vp, Vec3In, c_float_p, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp,
                                            vp]),
+    "sunsky_sequence_prepare_irradiance": (C.c_int, [vp, C.c_int, C.c_int, c_float_p, C.c_int]),
+    "sunsky_sequence_irradiance_info": (C.c_int, [vp, C.POINTER(SequenceIrradianceDesc)]),
+    "sunsky_sequence_get_irradiance_table": (C.c_int, [vp, C.c_int, c_float_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "sunsky_sequence_irradiance": (C.c_int, [vp, Vec3In, vp, C.c_size_t, vp, C.c_size_t, vp]),
     "sunsky_direct_diffuse": (C.c_int, [vp, Vec3In, vp, vp, C.c_int, C.c_size_t, C.c_uint32, C.c_uint32,
                                         vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp]),
     "sunsky_direct_diffuse_rays": (C.c_int, [vp, Vec3In, C.c_uint32, C.c_uint32, C.c_size_t, Vec3Out, Vec3Out,

@@ -229,6 +229,49 @@ class SunskySequence:
         check(lib().sunsky_sequence_pdf_direction(self._h, vin, _ptr(mask), n, _ptr(out), self._stream()))
         return out
 
+    # ------------------------------------------------------------ irradiance on receivers
+    def prepare_irradiance(self, n_z=64, n_phi=256, wavelengths=None):
+        """Builds the irradiance tables (sunsky_sequence_prepare_irradiance): the cumulative sky
+        per plane over an n_z x n_phi equal-solid-angle grid and one disc flux per frame and plane.
+        Planes: RGB, or one per entry of `wavelengths` (spectral, at most 32).  Host-synchronous;
+        a second call replaces the tables; independent of prepare_sampling.  Works on host-only
+        sequences."""
+        _, lam_p, m = self._lambda(wavelengths, "sequence prepare_irradiance")
+        check(lib().sunsky_sequence_prepare_irradiance(self._h, int(n_z), int(n_phi), lam_p, m))
+
+    def irradiance_info(self):
+        d = _capi.SequenceIrradianceDesc()
+        check(lib().sunsky_sequence_irradiance_info(self._h, C.byref(d)))
+        return {"n_z": d.n_z, "n_phi": d.n_phi, "n_planes": d.n_planes, "omega": d.omega}
+
+    def irradiance_table(self, name):
+        """One irradiance table as fp32: "sky" (P, n_z, n_phi), the cumulative sky R_p at the cell
+        centres (not multiplied by omega), or "sun_flux" (P, K), the disc fluxes F_k[p] (not
+        multiplied by the weights)."""
+        tid = _capi.SEQUENCE_IRRADIANCE_TABLES[name]
+        cnt = C.c_size_t()
+        check(lib().sunsky_sequence_get_irradiance_table(self._h, tid, None, 0, C.byref(cnt)))
+        buf = (C.c_float * cnt.value)()
+        check(lib().sunsky_sequence_get_irradiance_table(self._h, tid, buf, cnt.value, C.byref(cnt)))
+        a = np.array(buf, dtype=np.float32)
+        i = self.irradiance_info()
+        return a.reshape(i["n_planes"], i["n_z"], i["n_phi"]) if name == "sky" else a.reshape(i["n_planes"], -1)
+
+    def irradiance(self, normals, active=None, out=None):
+        """E_p(n) of the cumulative sky and suns on receivers with world-space normals (3, n) ->
+        (P, n): the fixed quadrature of sunsky_sequence_irradiance over the prepared tables.
+        Needs prepare_irradiance; `out` may have a row stride, as eval's."""
+        if self.device is None:
+            self.irradiance_info()   # an unprepared sequence says so first
+            raise ValueError("host-only sequence (over a host-only emitter) cannot launch kernels")
+        nrm, vin = SunskyEmitter._vec_in(self, normals)
+        n = nrm.shape[1]
+        planes = self.irradiance_info()["n_planes"]
+        out = SunskyEmitter._out(self, out, (planes, n), row_stride_ok=True)
+        mask = SunskyEmitter._mask(self, active, n)
+        check(lib().sunsky_sequence_irradiance(self._h, vin, _ptr(mask), n, _ptr(out), out.stride(0), self._stream()))
+        return out
+
     # ------------------------------------------------------------ gradients and updates
     def update(self, sun_directions=None, turbidity=None, weights=None):
         """Replaces the frames in place (sunsky_sequence_update): the same count, None keeps the

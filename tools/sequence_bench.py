@@ -12,7 +12,9 @@ does an eval's transcendental work with no HBM traffic).  Not part of bench.py.
                 sequence.eval at the sampled directions (see sampling()).
   --grad     -- instead: sequence.eval_vjp beside sequence.eval in reference precision and the
                 per-frame loop it replaces (see grad(); --no-loop leaves the loop out, for a
-                profiler run of the sequence kernels alone)."""
+                profiler run of the sequence kernels alone).
+  --irradiance -- instead: sequence.irradiance on 2^20 receivers beside the chunked torch
+                formulation a user writes from the read-back tables (see irradiance())."""
 import json
 import os
 import statistics
@@ -163,14 +165,68 @@ def grad(ks, dev, with_loop):
     print("sequence_bench grad done")
 
 
+def irradiance(ks, dev):
+    """--irradiance: E on n = 2^20 receivers with normals uniform on the sphere, RGB, 64 x 256
+    cells.  The yardstick of the same session is what a user writes today from the tables read
+    back once: relu(N_l D^T) @ (omega R)^T plus the sun term in torch, in chunks of 2^14 receivers
+    (an n x cells intermediate per chunk).  Prints both medians, their ratio, receiver-cell pairs
+    per second, prepare_irradiance's time and the largest difference of the two results."""
+    n, chunk = 1 << 20, 1 << 14
+    g = torch.Generator(device=dev).manual_seed(3)
+    v = torch.randn((3, n), device=dev, generator=g)
+    nrm = (v / v.norm(dim=0, keepdim=True)).contiguous()
+    base = {"type": "sunsky", "sun_direction": [0.3, 0.4, 0.866], "turbidity": 3.0, "albedo": 0.2}
+    for k in ks:
+        dirs, turb, wts = frames(k)
+        seq = ss.SunskySequence(ss.load_dict(dict(base)), dirs, turb, wts)
+        seq.prepare_irradiance()    # warm: module load, allocator
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        seq.prepare_irradiance()
+        t_prep = (time.perf_counter() - t0) * 1e3
+        info = seq.irradiance_info()
+        nz, nphi = info["n_z"], info["n_phi"]
+        # the tables read back once, as device tensors (an identity to_world: N_l = N)
+        z = (np.arange(nz) + 0.5) / nz
+        phi = (np.arange(nphi) + 0.5) * (2 * np.pi / nphi)
+        st = np.sqrt(1 - z * z)
+        D = np.stack([np.outer(st, np.cos(phi)).ravel(), np.outer(st, np.sin(phi)).ravel(), np.repeat(z, nphi)], 1)
+        D_t = torch.from_numpy(D.astype(np.float32)).to(dev)                                        # (cells, 3)
+        R_t = torch.from_numpy(info["omega"] * seq.irradiance_table("sky").reshape(3, -1)).to(dev)   # (3, cells)
+        S_t = torch.from_numpy(np.stack([seq.frame(i)["sun_dir_local"] for i in range(k)])).to(dev)  # (K, 3)
+        F_t = torch.from_numpy(wts[None, :] * seq.irradiance_table("sun_flux")).to(dev)              # (3, K)
+        out_t = torch.empty((3, n), device=dev)
+        out = torch.empty((3, n), device=dev)
+
+        def torch_chunks():
+            for a in range(0, n, chunk):
+                nl = nrm[:, a:a + chunk].t()
+                e = torch.relu(nl @ D_t.t()) @ R_t.t() + torch.relu(nl @ S_t.t()) @ F_t.t()
+                out_t[:, a:a + chunk] = e.t()
+
+        t_kernel, all_kernel = median_ms(lambda: seq.irradiance(nrm, out=out))
+        t_torch, all_torch = median_ms(torch_chunks)
+        diff = float(((out - out_t).abs().max() / out_t.abs().max()).item())
+        print(json.dumps({"K": k, "n": n, "table": [nz, nphi], "prepare_irradiance_ms": round(t_prep, 3),
+                          "irradiance_ms": round(t_kernel, 3), "torch_chunked_ms": round(t_torch, 3),
+                          "torch_over_kernel": round(t_torch / t_kernel, 2),
+                          "receiver_cell_pairs_per_s": round(n * nz * nphi / (t_kernel * 1e-3), 0),
+                          "max_diff_vs_torch_of_max": diff,
+                          "irradiance_ms_all": [round(t, 3) for t in all_kernel],
+                          "torch_chunked_ms_all": [round(t, 3) for t in all_torch]}), flush=True)
+    print("sequence_bench irradiance done")
+
+
 def main():
-    flags = ("--sampling", "--grad", "--no-loop")
+    flags = ("--sampling", "--grad", "--no-loop", "--irradiance")
     args = [a for a in sys.argv[1:] if a not in flags]
     ks = [int(a) for a in args] or [24, 365]
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     if "--sampling" in sys.argv[1:]:
         return sampling(ks, dev)
+    if "--irradiance" in sys.argv[1:]:
+        return irradiance(ks, dev)
     if "--grad" in sys.argv[1:]:
         return grad(ks, dev, "--no-loop" not in sys.argv[1:])
     g = torch.Generator(device=dev).manual_seed(3)
