@@ -19,7 +19,8 @@
  *     eval_direction, eval_spectral_broadcast, sample_direction, pdf_direction,
  *     sample_ray, sample_wavelengths, direct_diffuse, direct_diffuse_rays,
  *     eval_jvp_dir, eval_vjp_dir, sequence_eval, sequence_sample_direction,
- *     sequence_pdf_direction, sequence_eval_vjp, sequence_irradiance)
+ *     sequence_pdf_direction, sequence_eval_vjp, sequence_irradiance,
+ *     sequence_irradiance_vjp)
  *     allocate nothing, make no host-synchronous call and may be captured into
  *     a hipGraph (tests/test_graph_capture.py).  Kernels read the emitter state
  *     from device memory, which parameters_changed_async rewrites in place on
@@ -53,7 +54,8 @@ extern "C" {
                                         added since, additive only (the version stays 7):
                                         eval_jvp_dir, eval_vjp_dir; sun_coordinates and the
                                         sunsky_sequence_* calls (frame sequences, their
-                                        sampling, update, gradients and irradiance included) */
+                                        sampling, update, gradients, irradiance and the
+                                        irradiance's gradients included) */
 
 typedef enum sunsky_status {
     SUNSKY_OK = 0,
@@ -482,7 +484,9 @@ int sunsky_sequence_eval_vjp(const sunsky_sequence *seq, sunsky_vec3_in wi, cons
  * The sun is a directional source carrying the disc's flux, with the cosine taken at the disc
  * centre: for a disc wholly in front of the receiver that is off by at most 1 - cos_cutoff,
  * relative.  Only the upper local hemisphere contributes.  Out of scope: light reflected by the
- * ground, occlusion and visibility masks, gradients of E, per-receiver wavelength lists.
+ * ground, occlusion and visibility masks, per-receiver wavelength lists, and the gradients of E
+ * with respect to a frame's turbidity and sun direction (they need a tangent of the flux rule;
+ * the gradients with respect to the normals and the weights are below).
  * Inactive lanes (mask) give exact zeros.
  *
  * Summation order (the contract; independent of n, of the grid and of the lane, so two runs and
@@ -529,6 +533,78 @@ int sunsky_sequence_get_irradiance_table(const sunsky_sequence *seq, int id, flo
                                          size_t *count);
 int sunsky_sequence_irradiance(const sunsky_sequence *seq, sunsky_vec3_in normal, const uint8_t *active, size_t n,
                                float *out, size_t out_stride, void *stream);
+
+/* Gradients of the irradiance with respect to the receiver normals and the frame weights
+ * (reverse mode).  Notation as above, with A_p[i, j] = fp32(omega R_p[i, j]) and
+ * B_k[p] = fp32(w_k F_k[p]) (the staged image's values, rounded once at prepare time),
+ * P = n_planes, Q = n_z n_phi, K = count, a cotangent d_out[p, r] in the layout of
+ * sunsky_sequence_irradiance's out (a row stride d_stride is allowed) and
+ *     L = sum_r sum_p d_out[p, r] E_p(n_r).
+ * E is piecewise linear in n and linear in w, so both gradients are closed forms over the tables.
+ * Gradients with respect to a frame's turbidity and sun direction are out of scope: they need a
+ * tangent of the 4 x 16 flux rule, which is not defined.
+ *
+ * Normal gradient: per receiver, written (not accumulated), three world-space planes.
+ *     g_l(r) = sum_i sum_j a_r[i, j] c_ij [n_l . c_ij > 0] + sum_k b_r[k] s_k [n_l . s_k > 0],
+ *     a_r[i, j] = sum_p d_out[p, r] A_p[i, j],   b_r[k] = sum_p d_out[p, r] B_k[p],
+ *     grad_normal(r) = (to_local's linear part)^T g_l(r).
+ * The clamp's derivative is the strict step: a dot product of exactly 0 (or a NaN) contributes 0.
+ * The dot product is the forward's, fma(a.z, b.z, fma(a.y, b.y, a.x b.x)).  Summation order (the
+ * contract; independent of n, of the grid and of the lane), per component of g_l: per record the
+ * plane fold a = fma(d_out[p], value_p, a) from 0 in plane order, then fma(a or 0, direction,
+ * sum); a row's cells in column order into a row sum that starts at 0; the row sums in row order
+ * (row 0 first); then the suns of the staged image in frame order (frames whose w_k F_k is 0 in
+ * every plane are not in it).  The sequential depth is n_phi + n_z + count + n_planes fp32
+ * additions per component.  Inactive lanes (mask) get exact zeros.
+ *
+ * Weight gradient: accumulated (+=) into grad_weight[K], as sunsky_sequence_eval_vjp does.
+ *     grad_weight[k] += sum_r sum_p d_out[p, r] E^k_p(n_r),
+ *     E^k_p(n) = sum_ij omega sky_{k,p}(c_ij) max(0, n_l . c_ij) + F_k[p] max(0, n_l . s_k),
+ * sky_{k,p} frame k's term of R_p (reference precision, the disc branch off; spectral: the
+ * two-node lerp, an invalid wavelength a plane of zeros) and F_k the unweighted flux.  Every
+ * frame counts: one with w_k = 0 gets E^k (not 0), and so does one the forward's image leaves out
+ * because w_k F_k = 0.  A frame whose sun is below the horizon gets exactly 0; inactive lanes add
+ * exactly 0.  It is computed through the adjoint image, never as n x Q x K work:
+ *     G_p[i, j] = sum_r d_out[p, r] max(0, n_l,r . c_ij),   H_p[k] = sum_r d_out[p, r] max(0, n_l,r . s_k),
+ *     grad_weight[k] += omega sum_p sum_ij G_p[i, j] sky_{k,p}(c_ij) + sum_p H_p[k] F_k[p].
+ * The reduction is deterministic (no float atomics; two runs and any launch shape give the same
+ * bits) and its shape is fixed by (n, P, Q, K) and the workspace bound alone -- the grid, the CU
+ * count and SUNSKY_AMD_BLOCKS_PER_CU do not enter:
+ *   - The receivers are cut into slices.  slices_wanted = ceil(n / 1024), at most 64 and at most
+ *     floor(bound / (P (Q + K))) (at least 1); slice_len = ceil(n / slices_wanted) rounded up to a
+ *     multiple of 256; slices = ceil(n / slice_len), slice s = receivers [s slice_len, ..).
+ *   - Within a slice, per entry (cell or sun) and plane: chunks of 256 consecutive receivers;
+ *     a chunk's receivers in index order into a chunk sum that starts at 0,
+ *     fma(d_out[p, r], max(0, n_l,r . dir), chunk); the chunk sums in chunk order into the slice's
+ *     sum.  One workspace row of P (Q + K) floats per slice.
+ *   - The rows are added in slice order: ((row_0 + row_1) + row_2) + ...
+ *   - Per frame, 256 lanes: lane l adds its cells (cell = l + 256 t, t ascending) into one sum
+ *     that starts at 0, fma(G_p[cell], sky_{k,p}(cell), sum) -- RGB: a cell's three planes in
+ *     plane order; spectral: plane by plane, invalid wavelengths skipped --; the 64 lanes of a wave
+ *     by the fixed tree (lane l += lane l + off for off = 32, 16, .., 1); the 4 waves in wave
+ *     order; times omega; plus h, h = fma(H_p[k], F_k[p], h) from 0 in plane order.
+ * The sequential depth is m = 256 + slice_len / 256 + slices + P ceil(Q / 256) + P + 11 fp32
+ * additions (chunk, chunks, slices, lane, tree 6 + waves 3 + omega and h 2, suns).
+ *
+ * sunsky_sequence_prepare_irradiance_grad (host-synchronous; needs prepare_irradiance first)
+ * stages on the device what the forward's image lacks -- every frame's local sun direction and
+ * the unweighted F_k[p] -- and allocates the reduction workspace: at most 64 rows of P (Q + K)
+ * floats and at most 2^22 floats (16 MiB), or one row where that is more.  The environment
+ * variable SUNSKY_AMD_IRRADIANCE_GRAD_WORKSPACE_FLOATS, read at prepare time, lowers the 2^22.
+ * It is sticky: once called, a later prepare_irradiance restages it for the new tables;
+ * sunsky_sequence_update drops it together with the tables (prepare_irradiance brings both back).
+ * On a host-only sequence it is a state change only.
+ *
+ * sunsky_sequence_irradiance_vjp is a hot-path call: stream-ordered, no allocation, no
+ * host-synchronous call, capturable.  Either output may be NULL (grad_normal: all three planes);
+ * d_out must not be NULL; n == 0 succeeds and writes nothing; n <= 2^32 - 256.  Before
+ * prepare_irradiance_grad it fails with SUNSKY_ERROR_INVALID_VALUE and a message naming the
+ * missing call; a host-only sequence refuses it as the other launches do.  Calls on one sequence
+ * share the workspace: ordering them across streams is the caller's job. */
+int sunsky_sequence_prepare_irradiance_grad(sunsky_sequence *seq);
+int sunsky_sequence_irradiance_vjp(const sunsky_sequence *seq, sunsky_vec3_in normal, const uint8_t *active,
+                                   size_t n, const float *d_out, size_t d_stride, sunsky_vec3_out grad_normal,
+                                   float *grad_weight, void *stream);
 
 /* A caller of sample_direction / pdf_direction / eval: the sun-and-sky light a
  * smooth-diffuse point receives, gathered as the path integrator does at one vertex

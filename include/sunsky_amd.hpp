@@ -473,6 +473,17 @@ public:
         check(sunsky_sequence_irradiance(s_, sunsky_vec3_in{normal.x, normal.y, normal.z}, active, n, out.data,
                                          out.stride ? out.stride : n, stream));
     }
+    // Gradients of the irradiance with respect to the normals (written, three world-space
+    // planes) and the frame weights (accumulated into count floats); either may be left out
+    // (a default Vector3Out / nullptr).  Needs prepare_irradiance_grad, which is sticky.
+    void prepare_irradiance_grad() { check(sunsky_sequence_prepare_irradiance_grad(s_)); }
+    void irradiance_vjp(Vector3 normal, size_t n, const float* d_out, const Vector3Out& grad_normal, float* grad_weight,
+                        const uint8_t* active = nullptr, size_t d_stride = 0, void* stream = nullptr) const {
+        check(sunsky_sequence_irradiance_vjp(s_, sunsky_vec3_in{normal.x, normal.y, normal.z}, active, n, d_out,
+                                             d_stride ? d_stride : n,
+                                             sunsky_vec3_out{grad_normal.x, grad_normal.y, grad_normal.z}, grad_weight,
+                                             stream));
+    }
     // Per-frame gradients of the weighted sum (sunsky_amd.h).  update: empty = keep the current
     // values; the frame count does not change.
     struct FrameTangent {

@@ -170,6 +170,10 @@ void check_xform_form(hipModule_t mod, const std::string& path, bool want_identi
     X(SEQUENCE_EVAL_VJP_SPEC, "sunsky_sequence_eval_vjp_spec", kSeqGradBlocksPerCu, false, 1)      \
     X(SEQUENCE_IRRADIANCE_RGB, "sunsky_sequence_irradiance_rgb", 64, false, 2)                     \
     X(SEQUENCE_IRRADIANCE_SPEC, "sunsky_sequence_irradiance_spec", 64, false, 2)                   \
+    X(SEQUENCE_IRRADIANCE_VJP_NORMAL_RGB, "sunsky_sequence_irradiance_vjp_normal_rgb", 64, false, 2)   \
+    X(SEQUENCE_IRRADIANCE_VJP_NORMAL_SPEC, "sunsky_sequence_irradiance_vjp_normal_spec", 64, false, 2) \
+    X(SEQUENCE_IRRADIANCE_ADJOINT, "sunsky_sequence_irradiance_adjoint", kSeqIrrGradAdjointBlocksPerCu, false, 1) \
+    X(SEQUENCE_IRRADIANCE_GRAD_FOLD, "sunsky_sequence_irradiance_grad_fold", kSeqIrrGradFoldBlocksPerCu, false, 1) \
     X(DEBUG_SUN_SEGMENTS, "sunsky_debug_sun_segments", 16, false, 1)
 
 #define X(id, name, wg, dir, per) K_##id,
@@ -700,6 +704,13 @@ struct sunsky_sequence {
     std::vector<float> irr_sky, irr_flux;
     float* d_irr = nullptr;
     SeqIrradiance irr = {};
+    LambdaSet irr_L = {};                    // the spectral planes' wavelengths (the weight gradient's sky terms)
+    // gradients of the irradiance (prepare_irradiance_grad): asked for once (sticky: a later
+    // prepare_irradiance restages it), staged for the current tables when irr_grad_ready
+    bool irr_grad_wanted = false, irr_grad_ready = false;
+    float* d_irr_grad = nullptr;             // every frame's sun | F_k[p] | the reduction workspace
+    SeqIrrGrad irr_grad = {};
+    size_t irr_grad_cap = 0;                 // the workspace bound in floats, as read at prepare time
 
     void require_device() const {
         if (!mod) throw std::invalid_argument("host-only sequence (over a sunsky_emitter_create_host emitter) cannot launch kernels");
@@ -718,6 +729,12 @@ struct sunsky_sequence {
             throw std::invalid_argument("the sequence has no irradiance tables yet: call "
                                         "sunsky_sequence_prepare_irradiance first");
     }
+    void require_irradiance_grad() const {
+        require_irradiance();
+        if (!irr_grad_ready)
+            throw std::invalid_argument("the sequence's irradiance gradients are not prepared yet: call "
+                                        "sunsky_sequence_prepare_irradiance_grad first");
+    }
     // The snapshot never changes, so an identity to_world takes the identity code object under
     // capture too (SUNSKY_AMD_GENERAL_XFORM=1: the general one always)
     int xform_form() const {
@@ -732,7 +749,8 @@ struct sunsky_sequence {
         if (hipGetDevice(&cur) == hipSuccess && cur != device) (void)hipSetDevice(device);
         (void)hipDeviceSynchronize();   // launches in flight may still read the records
         for (void* p : {(void*)d_state, d_frames, (void*)d_sun_rad, (void*)d_sun_ld, (void*)d_bake, (void*)d_samp,
-                        (void*)d_sky_ds, d_grads, (void*)d_grad_stages, (void*)d_grad_rows, (void*)d_irr})
+                        (void*)d_sky_ds, d_grads, (void*)d_grad_stages, (void*)d_grad_rows, (void*)d_irr,
+                        (void*)d_irr_grad})
             if (p) (void)hipFree(p);
         if (bake_done) (void)hipEventDestroy(bake_done);
         if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
@@ -1184,6 +1202,49 @@ int seq_irradiance_image(const sunsky_sequence* q, int nz, int nphi, int planes,
     }
     image.resize((cells + (size_t)nsuns) * rec);
     return nsuns;
+}
+
+// The workspace bound of the irradiance gradients in floats: kSeqIrrGradWorkspaceFloats, or the
+// smaller value SUNSKY_AMD_IRRADIANCE_GRAD_WORKSPACE_FLOATS gives (read at every prepare).
+size_t seq_irr_grad_cap() {
+    size_t cap = kSeqIrrGradWorkspaceFloats;
+    if (const char* e = std::getenv("SUNSKY_AMD_IRRADIANCE_GRAD_WORKSPACE_FLOATS")) {
+        const long long v = std::atoll(e);
+        if (v >= 1 && (unsigned long long)v < cap) cap = (size_t)v;
+    }
+    return cap;
+}
+
+// What sunsky_sequence_irradiance_vjp reads beside the forward's image, for the tables as they
+// are now: every frame's local sun direction, the unweighted fluxes, and the workspace of the
+// most slices the bound allows.  A host-only sequence only changes state.
+void seq_stage_irradiance_grad(sunsky_sequence* q) {
+    q->irr_grad_ready = false;
+    if (q->device >= 0) {
+        if (q->d_irr_grad) hip_check(hipFree(q->d_irr_grad), "hipFree");
+        q->d_irr_grad = nullptr;
+        const int planes = q->irr_planes, count = q->count;
+        const size_t cells = (size_t)q->irr_nz * (size_t)q->irr_nphi, entries = cells + (size_t)count;
+        q->irr_grad_cap = seq_irr_grad_cap();
+        const size_t slices = seq_irr_grad_max_slices(planes, cells, count, q->irr_grad_cap);
+        const size_t head = 4 * (size_t)count + (size_t)planes * count;
+        std::vector<float> h(head, 0.f);
+        for (int k = 0; k < count; ++k) {
+            const SeqFrame<1>* f = seq_header(q, k);
+            for (int a = 0; a < 3; ++a) h[4 * (size_t)k + a] = f->sun_n[a];
+        }
+        std::copy(q->irr_flux.begin(), q->irr_flux.end(), h.begin() + 4 * (size_t)count);
+        hip_check(hipMalloc(&q->d_irr_grad, sizeof(float) * (head + slices * planes * entries)), "hipMalloc");
+        hip_check(hipMemcpy(q->d_irr_grad, h.data(), sizeof(float) * head, hipMemcpyHostToDevice), "hipMemcpy");
+        SeqIrrGrad& g = q->irr_grad;
+        std::memset(&g, 0, sizeof(g));
+        g.suns = q->d_irr_grad;
+        g.flux = q->d_irr_grad + 4 * (size_t)count;
+        g.rows = q->d_irr_grad + head;
+        g.omega = q->irr_omega;
+        g.count = count;
+    }
+    q->irr_grad_ready = true;
 }
 
 }  // namespace
@@ -1997,6 +2058,7 @@ int sunsky_sequence_update(sunsky_sequence* seq, const float* sun_dirs, const fl
         // the sampling distribution described the old frames
         seq->samp_nz = seq->samp_nphi = 0;
         seq->irr_nz = seq->irr_nphi = seq->irr_planes = 0;   // and so did the irradiance tables
+        seq->irr_grad_ready = false;                         // and what their gradients read (wanted stays)
         if (seq->grad_ready) seq_stage_grad(seq);
     });
 }
@@ -2390,7 +2452,10 @@ int sunsky_sequence_prepare_irradiance(sunsky_sequence* seq, int n_z, int n_phi,
             seq->irr_nz = n_z;
             seq->irr_nphi = n_phi;
             seq->irr_planes = planes;
+            seq->irr_L = T.L;
+            if (seq->irr_grad_wanted) seq_stage_irradiance_grad(seq);   // sticky: restaged for the new tables
         };
+        seq->irr_grad_ready = false;
         if (seq->device < 0) {
             seq_irradiance_host(seq, n_z, n_phi, T.L, planes, T.sin2_half_ap, sky, flux);
             accept();
@@ -2469,6 +2534,72 @@ int sunsky_sequence_irradiance(const sunsky_sequence* seq, sunsky_vec3_in nrm, c
         run_kernel(seq->mod, seq->xform_form(), seq->precision,
                    seq->variant == kSpectral ? K_SEQUENCE_IRRADIANCE_SPEC : K_SEQUENCE_IRRADIANCE_RGB, n, args,
                    (hipStream_t)stream);
+    });
+}
+
+int sunsky_sequence_prepare_irradiance_grad(sunsky_sequence* seq) {
+    SUNSKY_PHASE("InitScene", "sequence_prepare_irradiance_grad");
+    if (!seq) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sequence");
+    return guarded([&] {
+        seq->require_irradiance();
+        std::unique_ptr<DeviceScope> g;
+        if (seq->device >= 0) {
+            g.reset(new DeviceScope(seq->device));
+            hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");   // nothing may still use the old workspace
+        }
+        seq_stage_irradiance_grad(seq);
+        seq->irr_grad_wanted = true;
+    });
+}
+
+int sunsky_sequence_irradiance_vjp(const sunsky_sequence* seq, sunsky_vec3_in nrm, const uint8_t* active, size_t n,
+                                   const float* d_out, size_t d_stride, sunsky_vec3_out grad_normal, float* grad_weight,
+                                   void* stream) {
+    SUNSKY_PHASE("EndpointEvaluate", "sequence_irradiance_vjp");
+    if (!seq) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sequence");
+    if (n == 0) return SUNSKY_OK;
+    if (!nrm.x || !nrm.y || !nrm.z || !d_out) return fail(SUNSKY_ERROR_INVALID_VALUE, "null normal / d_out pointer");
+    if ((grad_normal.x != nullptr) != (grad_normal.y != nullptr) || (grad_normal.x != nullptr) != (grad_normal.z != nullptr))
+        return fail(SUNSKY_ERROR_INVALID_VALUE, "grad_normal must be all-NULL or all-set");
+    if (n > 0xffffff00ull) return fail(SUNSKY_ERROR_INVALID_VALUE, "more than 2^32 - 256 receivers");
+    return guarded([&] {
+        seq->require_irradiance_grad();   // first: the message names the missing call on any sequence
+        seq->require_device();
+        if (seq->irr_planes > 1 && d_stride < n) throw std::invalid_argument("d_stride < n");
+        DeviceScope g(seq->device);
+        const SunskyKArgs* K = seq->d_state;
+        SeqIrradiance S = seq->irr;
+        const bool spec = seq->variant == kSpectral;
+        const int form = seq->xform_form();
+        hipStream_t s = (hipStream_t)stream;
+        if (grad_normal.x) {
+            void* args[] = {&K, &S, (void*)&nrm.x, (void*)&nrm.y, (void*)&nrm.z, &active, &n, &d_out, &d_stride,
+                            (void*)&grad_normal.x, (void*)&grad_normal.y, (void*)&grad_normal.z};
+            run_kernel(seq->mod, form, seq->precision,
+                       spec ? K_SEQUENCE_IRRADIANCE_VJP_NORMAL_SPEC : K_SEQUENCE_IRRADIANCE_VJP_NORMAL_RGB, n, args, s);
+        }
+        if (!grad_weight) return;
+        const size_t cells = (size_t)seq->irr_nz * (size_t)seq->irr_nphi, entries = cells + (size_t)seq->count;
+        const SeqIrrGradShape shape = seq_irr_grad_shape(n, seq->irr_planes, cells, seq->count, seq->irr_grad_cap);
+        SeqIrrGrad G = seq->irr_grad;
+        G.dout = d_out;
+        G.dstride = d_stride;
+        G.slices = shape.slices;
+        G.slice_len = shape.slice_len;
+        const size_t tiles = (entries + kSeqIrrGradTile - 1) / kSeqIrrGradTile;
+        const size_t passes = spec ? (size_t)(seq->irr_planes + kSeqIrrGradSpecPlanes - 1) / kSeqIrrGradSpecPlanes : 1;
+        {   // one workgroup per work item (slice, tile, pass), grid-stride over the items
+            void* args[] = {&K, &S, &G, (void*)&nrm.x, (void*)&nrm.y, (void*)&nrm.z, &active, &n};
+            run_kernel(seq->mod, form, seq->precision, K_SEQUENCE_IRRADIANCE_ADJOINT,
+                       (size_t)shape.slices * tiles * passes * kBlock, args, s);
+        }
+        SeqArgs A = seq->args();
+        LambdaSet L = seq->irr_L;
+        for (int phase = shape.slices > 1 ? 0 : 1; phase < 2; ++phase) {
+            void* args[] = {&K, &A, &S, &G, &L, &phase, &grad_weight};
+            run_kernel(seq->mod, form, seq->precision, K_SEQUENCE_IRRADIANCE_GRAD_FOLD,
+                       phase == 0 ? (size_t)seq->irr_planes * entries : (size_t)seq->count * kBlock, args, s);
+        }
     });
 }
 

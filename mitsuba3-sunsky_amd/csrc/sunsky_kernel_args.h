@@ -270,4 +270,53 @@ struct SeqIrradiance {
 };
 static_assert(sizeof(SeqIrradiance) == 32 && offsetof(SeqIrradiance, nz) == 16, "SeqIrradiance layout");
 
+// ---------------------------------------------------------------- gradients of the sequence irradiance
+// sunsky_sequence_prepare_irradiance_grad / sunsky_sequence_irradiance_vjp (sunsky_amd.h has the
+// definition).  The weight gradient goes through the adjoint image: per slice of receivers one
+// workspace row [planes][cells + count] (G_p over the cells, then H_p over every frame's sun),
+// written by sunsky_sequence_irradiance_adjoint; sunsky_sequence_irradiance_grad_fold adds the
+// rows in slice order and contracts the sum with each frame's sky and flux.
+constexpr int kSeqIrrGradChunk = 256;          // receivers per chunk sum: one per lane of the workgroup that stages them
+constexpr int kSeqIrrGradCellsPerLane = 4;     // entries (cells or suns) a lane of the adjoint kernel owns
+constexpr int kSeqIrrGradTile = kSeqIrrGradChunk * kSeqIrrGradCellsPerLane;   // entries per workgroup
+constexpr int kSeqIrrGradSpecPlanes = 4;       // planes per pass of the adjoint kernel (spectral; RGB: 3, one pass)
+constexpr size_t kSeqIrrGradSliceMin = 1024;   // receivers: no slice is cut shorter
+constexpr unsigned kSeqIrrGradMaxSlices = 64;
+constexpr size_t kSeqIrrGradWorkspaceFloats = (size_t)1 << 22;   // 16 MiB: the cap of slices x planes x (cells + count)
+constexpr int kSeqIrrGradAdjointBlocksPerCu = 8, kSeqIrrGradFoldBlocksPerCu = 8;
+
+// The slices of n receivers: their number and length, a function of (n, planes, cells, count)
+// and the workspace bound only.  slices = ceil(n / kSeqIrrGradSliceMin) capped by
+// kSeqIrrGradMaxSlices and by the rows the bound holds (never below 1); the length is
+// ceil(n / slices) rounded up to whole chunks, and the slices in use are ceil(n / length).
+struct SeqIrrGradShape {
+    unsigned slices, slice_len;
+};
+inline unsigned seq_irr_grad_max_slices(int planes, size_t cells, int count, size_t cap_floats) {
+    const size_t row = (size_t)planes * (cells + (size_t)count), fit = cap_floats / row;
+    return (unsigned)(fit < 1 ? 1 : fit < kSeqIrrGradMaxSlices ? fit : kSeqIrrGradMaxSlices);
+}
+inline SeqIrrGradShape seq_irr_grad_shape(size_t n, int planes, size_t cells, int count, size_t cap_floats) {
+    const size_t most = seq_irr_grad_max_slices(planes, cells, count, cap_floats);
+    size_t want = (n + kSeqIrrGradSliceMin - 1) / kSeqIrrGradSliceMin;
+    want = want < 1 ? 1 : want < most ? want : most;
+    size_t len = (n + want - 1) / want;
+    len = (len + kSeqIrrGradChunk - 1) / kSeqIrrGradChunk * kSeqIrrGradChunk;
+    if (len < (size_t)kSeqIrrGradChunk) len = kSeqIrrGradChunk;
+    return SeqIrrGradShape{(unsigned)((n + len - 1) / len), (unsigned)len};
+}
+
+// What the three gradient kernels read beside the forward's image
+struct SeqIrrGrad {
+    const float* suns;         // [count] x {s_k.xyz, 0}: every frame's local sun direction
+    const float* flux;         // [planes][count] F_k[p], unweighted
+    float* rows;               // workspace [slices][planes][cells + count]
+    const float* dout;         // cotangent planes
+    size_t dstride;
+    float omega;
+    int count;
+    unsigned slices, slice_len;
+};
+static_assert(sizeof(SeqIrrGrad) == 56 && offsetof(SeqIrrGrad, omega) == 40, "SeqIrrGrad layout");
+
 }  // namespace sunsky

@@ -71,6 +71,19 @@ SEQUENCE_TABLES = {"sky": 0, "row_cdf": 1, "cell_cdf": 2, "q": 3, "frame_cdf": 4
 # sunsky_sequence_eval_vjp's launch shape (csrc/sunsky_kernel_args.h): workgroups per CU, the
 # workspace bound in floats, the frame count up to which a wave's row lives in LDS
 SEQ_GRAD_BLOCKS_PER_CU, SEQ_GRAD_WORKSPACE_FLOATS, SEQ_GRAD_LDS_FRAMES = 16, 1 << 22, 512
+# sunsky_sequence_irradiance_vjp's reduction shape (csrc/sunsky_kernel_args.h, include/sunsky_amd.h):
+# receivers per chunk, the shortest slice, the most slices, the workspace bound in floats and the
+# environment variable that lowers it
+SEQ_IRR_GRAD_CHUNK, SEQ_IRR_GRAD_SLICE_MIN, SEQ_IRR_GRAD_MAX_SLICES, SEQ_IRR_GRAD_WORKSPACE_FLOATS = 256, 1024, 64, 1 << 22
+SEQ_IRR_GRAD_WORKSPACE_ENV = "SUNSKY_AMD_IRRADIANCE_GRAD_WORKSPACE_FLOATS"
+
+
+def seq_irr_grad_shape(n, planes, cells, count, cap=SEQ_IRR_GRAD_WORKSPACE_FLOATS):
+    """(slices, slice_len) of n receivers, as sunsky_sequence_irradiance_vjp cuts them."""
+    most = max(1, min(SEQ_IRR_GRAD_MAX_SLICES, cap // (planes * (cells + count))))
+    want = max(1, min(most, -(-n // SEQ_IRR_GRAD_SLICE_MIN)))
+    length = max(1, -(-(-(-n // want)) // SEQ_IRR_GRAD_CHUNK)) * SEQ_IRR_GRAD_CHUNK
+    return -(-n // length), length
 
 _SIGS = {
     "sunsky_abi_version": (C.c_int, []),
@@ -137,6 +150,8 @@ _SIGS = {
     "sunsky_sequence_irradiance_info": (C.c_int, [vp, C.POINTER(SequenceIrradianceDesc)]),
     "sunsky_sequence_get_irradiance_table": (C.c_int, [vp, C.c_int, c_float_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sunsky_sequence_irradiance": (C.c_int, [vp, Vec3In, vp, C.c_size_t, vp, C.c_size_t, vp]),
+    "sunsky_sequence_prepare_irradiance_grad": (C.c_int, [vp]),
+    "sunsky_sequence_irradiance_vjp": (C.c_int, [vp, Vec3In, vp, C.c_size_t, vp, C.c_size_t, Vec3Out, vp, vp]),
     "sunsky_direct_diffuse": (C.c_int, [vp, Vec3In, vp, vp, C.c_int, C.c_size_t, C.c_uint32, C.c_uint32,
                                         vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp]),
     "sunsky_direct_diffuse_rays": (C.c_int, [vp, Vec3In, C.c_uint32, C.c_uint32, C.c_size_t, Vec3Out, Vec3Out,

@@ -16,6 +16,10 @@ differentiable function of the frames: the forward writes the given tensors' val
 sequence (seq.update, host-synchronous) and evaluates it, the backward is seq.eval_vjp.  The
 same caveats hold: the backward reads the sequence as it is when backward() runs, so do not
 update it (or call sequence_eval on it again) between a forward and its backward.
+
+sequence_irradiance(seq, normals, weights, ...) is seq.irradiance(normals) as a differentiable
+function of the receiver normals and the frame weights: the backward is seq.irradiance_vjp, with
+the same caveat.
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -78,6 +82,55 @@ class _SequenceEval(torch.autograd.Function):
             seq.eval_vjp(wi, d_out.contiguous(), ctx.wavelengths, ctx.active, grad=grad)
         return (None, None, None, None) + tuple(None if grad[key] is None else grad[key].to(dev)
                                                 for key, dev in zip(keys, ctx.devices))
+
+
+class _SequenceIrradiance(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, normals, seq, active, weights):
+        nrm = normals.detach()
+        ctx.seq, ctx.active = seq, active
+        ctx.weights_device = weights.device if weights is not None else None
+        ctx.save_for_backward(nrm)
+        if weights is not None:
+            if seq.irradiance_args is None:
+                raise ValueError("sequence_irradiance needs seq.prepare_irradiance(...) first: it prepares again "
+                                 "with the same arguments after it has updated the weights")
+            seq.update(weights=weights)
+            n_z, n_phi, lam = seq.irradiance_args
+            seq.prepare_irradiance(n_z, n_phi, lam)
+        if (ctx.needs_input_grad[0] or ctx.needs_input_grad[3]) and not seq.irradiance_grad_prepared:
+            seq.prepare_irradiance_grad()
+        return seq.irradiance(nrm, active)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_out):
+        (nrm,) = ctx.saved_tensors
+        seq = ctx.seq
+        need_n, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[3]
+        grad = {"normals": torch.empty_like(nrm) if need_n else None,
+                "weights": torch.zeros(len(seq), dtype=torch.float32, device=seq.device) if need_w else None}
+        if need_n or need_w:
+            d = d_out if d_out.dim() == 2 and (d_out.shape[1] <= 1 or d_out.stride(1) == 1) else d_out.contiguous()
+            seq.irradiance_vjp(nrm, d, ctx.active, grad=grad)
+        gw = grad["weights"]
+        return grad["normals"], None, None, None if gw is None else gw.to(ctx.weights_device)
+
+
+def sequence_irradiance(seq, normals, weights=None, active=None):
+    """seq.irradiance(normals, active), differentiable in the normals and in the frame weights.
+
+    normals: (3, n) float32 tensor on the sequence's device.  weights: a (K,) float32 tensor (any
+    device; its values are read on the host) or None to leave the sequence's weights as they are.
+    With weights the forward calls seq.update(weights=...) and seq.prepare_irradiance with the
+    arguments of the last prepare_irradiance; it returns bit for bit seq.irradiance's value.  The
+    backward is seq.irradiance_vjp: gradients for the normals and, on the weights' device, for the
+    weights.  Do not update the sequence between a forward and its backward."""
+    if not isinstance(normals, torch.Tensor) or normals.dtype != torch.float32 or normals.dim() != 2 or normals.shape[0] != 3:
+        raise ValueError("normals must be a float32 tensor of shape (3, n)")
+    if weights is not None and (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32):
+        raise ValueError("weights must be a float32 tensor or None")
+    return _SequenceIrradiance.apply(normals, seq, active, weights)
 
 
 def sequence_eval(seq, wi, weights=None, turbidity=None, sun_directions=None, wavelengths=None, active=None):

@@ -45,6 +45,8 @@ class SunskySequence:
     def __init__(self, em, sun_directions, turbidity=None, weights=None):
         self._h = None
         self.grad_prepared = False
+        self.irradiance_args = None            # (n_z, n_phi, wavelengths) of the last prepare_irradiance
+        self.irradiance_grad_prepared = False
         d = self._dirs(sun_directions)
         k = d.shape[0]
         t, w = self._per_frame(turbidity, k, "turbidity"), self._per_frame(weights, k, "weights")
@@ -238,6 +240,54 @@ class SunskySequence:
         sequences."""
         _, lam_p, m = self._lambda(wavelengths, "sequence prepare_irradiance")
         check(lib().sunsky_sequence_prepare_irradiance(self._h, int(n_z), int(n_phi), lam_p, m))
+        # what sequence_irradiance prepares again with after it has updated the weights
+        self.irradiance_args = (int(n_z), int(n_phi), None if lam_p is None else [float(x) for x in lam_p])
+
+    def prepare_irradiance_grad(self):
+        """Stages what irradiance_vjp reads beside the tables and allocates its bounded reduction
+        workspace (sunsky_sequence_prepare_irradiance_grad).  Needs prepare_irradiance; sticky: a
+        later prepare_irradiance restages it, update() drops it with the tables.  Host-synchronous;
+        a state change only on host-only sequences."""
+        check(lib().sunsky_sequence_prepare_irradiance_grad(self._h))
+        self.irradiance_grad_prepared = True
+
+    def irradiance_vjp(self, normals, d_out, active=None, grad=None):
+        """Reverse mode of irradiance(): with L = sum(d_out * irradiance(normals)), returns
+        {"normals": (3, n) dL/dn, written, "weights": (K,) dL/dw_k, accumulated} as device tensors
+        -- those of `grad` (an entry set to None is not computed) or new ones.  E is piecewise
+        linear in n (the clamp's derivative is the strict step) and linear in w; every frame gets
+        its weight gradient, a zero-weight one included.  Needs prepare_irradiance_grad.
+        Deterministic; calls on one sequence share a workspace, so order them across streams."""
+        if self.device is None:
+            # the library refuses, and says first which preparation is missing; it reads no pointer
+            p = C.cast((C.c_float * 1)(), C.c_void_p)
+            check(lib().sunsky_sequence_irradiance_vjp(self._h, Vec3In(p, p, p), None, 1, p, 1,
+                                                       _capi.Vec3Out(None, None, None), None, None))
+            raise ValueError("host-only sequence (over a host-only emitter) cannot launch kernels")
+        nrm, vin = SunskyEmitter._vec_in(self, normals)
+        n = nrm.shape[1]
+        planes = self.irradiance_info()["n_planes"]
+        mask = SunskyEmitter._mask(self, active, n)
+        d_out = torch.as_tensor(d_out, dtype=torch.float32, device=self.device)
+        if tuple(d_out.shape) != (planes, n):
+            raise ValueError(f"d_out must have shape ({planes}, {n})")
+        if n > 1 and d_out.stride(1) != 1 or planes > 1 and d_out.stride(0) < n:
+            d_out = d_out.contiguous()   # rows must be contiguous; a row stride is passed on as it is
+        count = len(self)
+        shapes = {"normals": (3, n), "weights": (count,)}
+        if grad is None:
+            grad = {"normals": torch.empty((3, n), dtype=torch.float32, device=self.device),
+                    "weights": torch.zeros(count, dtype=torch.float32, device=self.device)}
+        for key, shape in shapes.items():
+            g = grad.get(key)
+            if g is not None and (not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or g.device != self.device
+                                  or tuple(g.shape) != shape or not g.is_contiguous()):
+                raise ValueError(f"grad['{key}'] must be a contiguous float32 tensor of shape {shape} on {self.device}")
+        gn, gw = grad.get("normals"), grad.get("weights")
+        gout = _capi.Vec3Out(None, None, None) if gn is None else _capi.Vec3Out(*[gn[i].data_ptr() for i in range(3)])
+        check(lib().sunsky_sequence_irradiance_vjp(self._h, vin, _ptr(mask), n, _ptr(d_out), max(d_out.stride(0), n),
+                                                   gout, _ptr(gw), self._stream()))
+        return grad
 
     def irradiance_info(self):
         d = _capi.SequenceIrradianceDesc()

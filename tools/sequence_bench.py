@@ -14,7 +14,9 @@ does an eval's transcendental work with no HBM traffic).  Not part of bench.py.
                 per-frame loop it replaces (see grad(); --no-loop leaves the loop out, for a
                 profiler run of the sequence kernels alone).
   --irradiance -- instead: sequence.irradiance on 2^20 receivers beside the chunked torch
-                formulation a user writes from the read-back tables (see irradiance())."""
+                formulation a user writes from the read-back tables (see irradiance()).
+  --irradiance-grad -- instead: sequence.irradiance_vjp beside sequence.irradiance and the torch
+                formulations of both gradients (see irradiance_grad())."""
 import json
 import os
 import statistics
@@ -217,8 +219,105 @@ def irradiance(ks, dev):
     print("sequence_bench irradiance done")
 
 
+def irradiance_grad(ks, dev):
+    """--irradiance-grad: sequence.irradiance_vjp on irradiance()'s workload (n = 2^20 normals on the
+    sphere, RGB, 64 x 256 cells) with a standard-normal cotangent: the normal gradient alone, the
+    weight gradient alone and both.  Two yardsticks of the same session: (a) sequence.irradiance at
+    the same n; (b) what a user writes today -- normals: torch autograd through irradiance()'s
+    chunked formulation; weights: a (K P) x cells per-frame table read back from K one-hot
+    sequences (timed once, apart), then relu(N_l D^T) @ table^T contracted with the cotangent, in
+    chunks.  Prints the medians, the ratios and the largest differences of the results."""
+    n, chunk = 1 << 20, 1 << 14
+    g = torch.Generator(device=dev).manual_seed(3)
+    v = torch.randn((3, n), device=dev, generator=g)
+    nrm = (v / v.norm(dim=0, keepdim=True)).contiguous()
+    d_out = torch.randn((3, n), device=dev, generator=g)
+    base = {"type": "sunsky", "sun_direction": [0.3, 0.4, 0.866], "turbidity": 3.0, "albedo": 0.2}
+    for k in ks:
+        dirs, turb, wts = frames(k)
+        seq = ss.SunskySequence(ss.load_dict(dict(base)), dirs, turb, wts)
+        seq.prepare_irradiance()
+        t0 = time.perf_counter()
+        seq.prepare_irradiance_grad()
+        t_prep = (time.perf_counter() - t0) * 1e3
+        info = seq.irradiance_info()
+        nz, nphi, omega = info["n_z"], info["n_phi"], info["omega"]
+        z = (np.arange(nz) + 0.5) / nz
+        phi = (np.arange(nphi) + 0.5) * (2 * np.pi / nphi)
+        st = np.sqrt(1 - z * z)
+        D = np.stack([np.outer(st, np.cos(phi)).ravel(), np.outer(st, np.sin(phi)).ravel(), np.repeat(z, nphi)], 1)
+        D_t = torch.from_numpy(D.astype(np.float32)).to(dev)                                        # (cells, 3)
+        R_t = torch.from_numpy(omega * seq.irradiance_table("sky").reshape(3, -1)).to(dev)          # (3, cells)
+        S_t = torch.from_numpy(np.stack([seq.frame(i)["sun_dir_local"] for i in range(k)])).to(dev)  # (K, 3)
+        flux = seq.irradiance_table("sun_flux")                                                      # (3, K)
+        F_t = torch.from_numpy(wts[None, :] * flux).to(dev)
+        # (b) weights: the per-frame tables from one-hot sequences, once
+        t0 = time.perf_counter()
+        one = ss.SunskySequence(ss.load_dict(dict(base)), dirs, turb, wts)
+        rows = []
+        for i in range(k):
+            one.update(weights=np.eye(k, dtype=np.float32)[i])
+            one.prepare_irradiance()
+            rows.append(omega * one.irradiance_table("sky").reshape(3, -1))
+        T_t = torch.from_numpy(np.stack(rows).astype(np.float32)).to(dev)                           # (K, 3, cells)
+        torch.cuda.synchronize()
+        t_tables = (time.perf_counter() - t0) * 1e3
+        Fk_t = torch.from_numpy(np.ascontiguousarray(flux.T)).to(dev)                                # (K, 3)
+        out = torch.empty((3, n), device=dev)
+        gn, gw = torch.empty((3, n), device=dev), torch.zeros(k, device=dev)
+        gn_t, gw_t = torch.empty((3, n), device=dev), torch.zeros(k, device=dev)
+
+        def torch_normals():
+            for a in range(0, n, chunk):
+                nl = nrm[:, a:a + chunk].t().detach().requires_grad_(True)
+                e = torch.relu(nl @ D_t.t()) @ R_t.t() + torch.relu(nl @ S_t.t()) @ F_t.t()
+                (e * d_out[:, a:a + chunk].t()).sum().backward()
+                gn_t[:, a:a + chunk] = nl.grad.t()
+
+        def torch_weights():
+            gw_t.zero_()
+            for a in range(0, n, chunk):
+                nl, dd = nrm[:, a:a + chunk].t(), d_out[:, a:a + chunk].t()                          # (c, 3) each
+                ek = (torch.relu(nl @ D_t.t()) @ T_t.reshape(3 * k, -1).t()).reshape(-1, k, 3)       # (c, K, 3)
+                ek = ek + torch.relu(nl @ S_t.t())[:, :, None] * Fk_t[None]
+                gw_t.add_((ek * dd[:, None, :]).sum((0, 2)))
+
+        def vjp_weights():
+            gw.zero_()
+            seq.irradiance_vjp(nrm, d_out, grad={"normals": None, "weights": gw})
+
+        t_fwd, all_fwd = median_ms(lambda: seq.irradiance(nrm, out=out))
+        t_n, all_n = median_ms(lambda: seq.irradiance_vjp(nrm, d_out, grad={"normals": gn, "weights": None}))
+        t_w, all_w = median_ms(vjp_weights)
+        t_both, all_both = median_ms(lambda: seq.irradiance_vjp(nrm, d_out, grad={"normals": gn, "weights": gw}))
+        t_tn, all_tn = median_ms(torch_normals)
+        t_tw, all_tw = median_ms(torch_weights)
+        vjp_weights()
+        torch.cuda.synchronize()
+        pairs = n * (nz * nphi + k)
+        print(json.dumps({"K": k, "n": n, "table": [nz, nphi], "prepare_irradiance_grad_ms": round(t_prep, 3),
+                          "irradiance_ms": round(t_fwd, 3), "vjp_normals_ms": round(t_n, 3),
+                          "vjp_weights_ms": round(t_w, 3), "vjp_both_ms": round(t_both, 3),
+                          "normals_over_forward": round(t_n / t_fwd, 2), "weights_over_forward": round(t_w / t_fwd, 2),
+                          "both_over_forward": round(t_both / t_fwd, 2),
+                          "torch_normals_ms": round(t_tn, 3), "torch_weights_ms": round(t_tw, 3),
+                          "torch_weights_tables_once_ms": round(t_tables, 1),
+                          "torch_over_vjp_normals": round(t_tn / t_n, 2), "torch_over_vjp_weights": round(t_tw / t_w, 2),
+                          "normals_pairs_per_s": round(pairs / (t_n * 1e-3), 0),
+                          "weights_pairs_per_s": round(pairs / (t_w * 1e-3), 0),
+                          "max_diff_normals_of_max": float(((gn - gn_t).abs().max() / gn_t.abs().max()).item()),
+                          "max_diff_weights_of_max": float(((gw - gw_t).abs().max() / gw_t.abs().max()).item()),
+                          "irradiance_ms_all": [round(t, 3) for t in all_fwd],
+                          "vjp_normals_ms_all": [round(t, 3) for t in all_n],
+                          "vjp_weights_ms_all": [round(t, 3) for t in all_w],
+                          "vjp_both_ms_all": [round(t, 3) for t in all_both],
+                          "torch_normals_ms_all": [round(t, 3) for t in all_tn],
+                          "torch_weights_ms_all": [round(t, 3) for t in all_tw]}), flush=True)
+    print("sequence_bench irradiance-grad done")
+
+
 def main():
-    flags = ("--sampling", "--grad", "--no-loop", "--irradiance")
+    flags = ("--sampling", "--grad", "--no-loop", "--irradiance", "--irradiance-grad")
     args = [a for a in sys.argv[1:] if a not in flags]
     ks = [int(a) for a in args] or [24, 365]
     dev = torch.device("cuda", 0)
@@ -227,6 +326,8 @@ def main():
         return sampling(ks, dev)
     if "--irradiance" in sys.argv[1:]:
         return irradiance(ks, dev)
+    if "--irradiance-grad" in sys.argv[1:]:
+        return irradiance_grad(ks, dev)
     if "--grad" in sys.argv[1:]:
         return grad(ks, dev, "--no-loop" not in sys.argv[1:])
     g = torch.Generator(device=dev).manual_seed(3)
