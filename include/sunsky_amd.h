@@ -20,7 +20,7 @@
  *     sample_ray, sample_wavelengths, direct_diffuse, direct_diffuse_rays,
  *     eval_jvp_dir, eval_vjp_dir, sequence_eval, sequence_sample_direction,
  *     sequence_pdf_direction, sequence_eval_vjp, sequence_irradiance,
- *     sequence_irradiance_vjp)
+ *     sequence_irradiance_horizon, sequence_irradiance_vjp)
  *     allocate nothing, make no host-synchronous call and may be captured into
  *     a hipGraph (tests/test_graph_capture.py).  Kernels read the emitter state
  *     from device memory, which parameters_changed_async rewrites in place on
@@ -54,8 +54,9 @@ extern "C" {
                                         added since, additive only (the version stays 7):
                                         eval_jvp_dir, eval_vjp_dir; sun_coordinates and the
                                         sunsky_sequence_* calls (frame sequences, their
-                                        sampling, update, gradients, irradiance and the
-                                        irradiance's gradients included) */
+                                        sampling, update, gradients, irradiance, the
+                                        irradiance's gradients and the irradiance under a
+                                        horizon profile included) */
 
 typedef enum sunsky_status {
     SUNSKY_OK = 0,
@@ -484,7 +485,8 @@ int sunsky_sequence_eval_vjp(const sunsky_sequence *seq, sunsky_vec3_in wi, cons
  * The sun is a directional source carrying the disc's flux, with the cosine taken at the disc
  * centre: for a disc wholly in front of the receiver that is off by at most 1 - cos_cutoff,
  * relative.  Only the upper local hemisphere contributes.  Out of scope: light reflected by the
- * ground, occlusion and visibility masks, per-receiver wavelength lists, and the gradients of E
+ * ground, occlusion other than a horizon profile (sunsky_sequence_irradiance_horizon below; no
+ * near-field or per-cell visibility masks), per-receiver wavelength lists, and the gradients of E
  * with respect to a frame's turbidity and sun direction (they need a tangent of the flux rule;
  * the gradients with respect to the normals and the weights are below).
  * Inactive lanes (mask) give exact zeros.
@@ -533,6 +535,56 @@ int sunsky_sequence_get_irradiance_table(const sunsky_sequence *seq, int id, flo
                                          size_t *count);
 int sunsky_sequence_irradiance(const sunsky_sequence *seq, sunsky_vec3_in normal, const uint8_t *active, size_t n,
                                float *out, size_t out_stride, void *stream);
+
+/* The irradiance under a horizon profile: far shading, per azimuth sector the elevation below
+ * which a receiver sees nothing (hills, the building across the street, the next row of panels).
+ * Additive: sunsky_sequence_irradiance and its bits are untouched.
+ *
+ * A profile has H = n_sectors azimuth sectors in the emitter's local frame; H divides n_phi, and
+ * sector b covers the columns [b n_phi / H, (b + 1) n_phi / H) of the prepared grid.  Its value
+ * h[b] = sin(horizon elevation) is in z units and used as given in fp32.  Profiles come as H planes,
+ * sector b's at horizon + b * horizon_stride: either one shared profile (n_profiles = 1: element 0
+ * of each plane is every receiver's, the site's far horizon) or one per receiver (n_profiles = n:
+ * element r of plane b is receiver r's).  With A_p = fp32(omega R_p) and B_k[p] = fp32(w_k F_k[p])
+ * the staged image's values,
+ *     v_r[i, b] = min(max(fma(-h_r[b], (float)n_z, (float)(i + 1)), 0), 1)
+ *     E_p(n_r; h_r) = sum_i sum_j fp32(max(0, n_l . c_ij) v_r[i, b(j)]) A_p[i, j]
+ *                   + sum_k [s_k.z >= h_r[b_k]] max(0, n_l . s_k) B_k[p].
+ * v is the visible share of row i's cells in sector b: the grid has equal solid angle in z, so
+ * the share of a cell above a horizon at height h is exactly linear in h.  The dot product and
+ * the summation order are sunsky_sequence_irradiance's (a row's cells in column order into a row
+ * sum from 0, the row sums in row order, then the image's suns in frame order, every
+ * product-and-add one fma); the only addition is that the clamped cosine is multiplied by v and
+ * rounded to fp32 before the fma.  The sun is a point source here: the test is the exact fp32
+ * comparison s_k.z >= h (equality counts as visible), and a hidden sun adds nothing.  b_k is the
+ * sector of sun k's column, b_k = j_k / (n_phi / H); j_k is staged at prepare_irradiance time on
+ * the host: phi = atan2f(s_k.y, s_k.x), plus 2 pi when negative, then
+ * j_k = min(max((int)(phi (float)n_phi / 2 pi), 0), n_phi - 1) -- the column the sampling table
+ * takes for a direction; a sun at the pole has column 0.
+ * sunsky_sequence_get_irradiance_sun_columns returns j_k for all count frames (those the image
+ * leaves out included); it works on host-only sequences, and sunsky_sequence_update drops the
+ * columns with the tables.
+ *
+ * Consequences.  h <= 0 in every sector gives sunsky_sequence_irradiance bit for bit (v = 1,
+ * c 1 = c, and every sun of the image has z >= 0).  h > 1 in every sector gives exact zeros.  A NaN
+ * in a profile is unspecified for that receiver only.  Inactive lanes give exact zeros.  The result
+ * does not depend on n, on the grid or on the lane; a shared profile gives the bits of the same
+ * profile repeated per receiver.
+ *
+ * Out of scope: gradients under a horizon (sunsky_sequence_irradiance_vjp is the unoccluded one),
+ * partial shading of a sun disc, near-field or per-cell visibility bitmaps, ground reflection,
+ * and profiles whose H does not divide n_phi (the caller picks n_phi: 240 for 48 sectors).
+ *
+ * A hot-path call: stream-ordered, no allocation, no host-synchronous call, capturable.
+ * n == 0 succeeds (nothing else is looked at); n < 2^32.  Refused with
+ * SUNSKY_ERROR_INVALID_VALUE and a message, in this order: a NULL normal or out; a NULL horizon;
+ * n >= 2^32; a sequence without prepare_irradiance; n_sectors < 1 or not a divisor of n_phi;
+ * n_profiles other than 1 and n; horizon_stride < n with n_profiles == n and n_sectors > 1;
+ * out_stride < n with more than one plane; a host-only sequence, as for the other launches. */
+int sunsky_sequence_get_irradiance_sun_columns(const sunsky_sequence *seq, int *out, size_t capacity, size_t *count);
+int sunsky_sequence_irradiance_horizon(const sunsky_sequence *seq, sunsky_vec3_in normal, const float *horizon,
+                                       int n_sectors, size_t n_profiles, size_t horizon_stride,
+                                       const uint8_t *active, size_t n, float *out, size_t out_stride, void *stream);
 
 /* Gradients of the irradiance with respect to the receiver normals and the frame weights
  * (reverse mode).  Notation as above, with A_p[i, j] = fp32(omega R_p[i, j]) and

@@ -473,6 +473,25 @@ public:
         check(sunsky_sequence_irradiance(s_, sunsky_vec3_in{normal.x, normal.y, normal.z}, active, n, out.data,
                                          out.stride ? out.stride : n, stream));
     }
+    // The irradiance under a horizon profile (sunsky_amd.h): n_sectors planes of sin(horizon
+    // elevation), sector b's at horizon + b * horizon_stride (0: packed -- 1 for a shared profile,
+    // n for per-receiver ones); per_receiver: element r of a plane is receiver r's, else element 0
+    // is everyone's.  irradiance_sun_columns: the grid column of every frame's sun.
+    void irradiance_horizon(Vector3 normal, size_t n, const float* horizon, int n_sectors, bool per_receiver,
+                            SpectrumOut out, const uint8_t* active = nullptr, size_t horizon_stride = 0,
+                            void* stream = nullptr) const {
+        check(sunsky_sequence_irradiance_horizon(s_, sunsky_vec3_in{normal.x, normal.y, normal.z}, horizon, n_sectors,
+                                                 per_receiver ? n : 1,
+                                                 horizon_stride ? horizon_stride : per_receiver ? n : 1, active, n,
+                                                 out.data, out.stride ? out.stride : n, stream));
+    }
+    std::vector<int> irradiance_sun_columns() const {
+        size_t count = 0;
+        check(sunsky_sequence_get_irradiance_sun_columns(s_, nullptr, 0, &count));
+        std::vector<int> c(count);
+        check(sunsky_sequence_get_irradiance_sun_columns(s_, c.data(), count, &count));
+        return c;
+    }
     // Gradients of the irradiance with respect to the normals (written, three world-space
     // planes) and the frame weights (accumulated into count floats); either may be left out
     // (a default Vector3Out / nullptr).  Needs prepare_irradiance_grad, which is sticky.

@@ -170,6 +170,8 @@ void check_xform_form(hipModule_t mod, const std::string& path, bool want_identi
     X(SEQUENCE_EVAL_VJP_SPEC, "sunsky_sequence_eval_vjp_spec", kSeqGradBlocksPerCu, false, 1)      \
     X(SEQUENCE_IRRADIANCE_RGB, "sunsky_sequence_irradiance_rgb", 64, false, 2)                     \
     X(SEQUENCE_IRRADIANCE_SPEC, "sunsky_sequence_irradiance_spec", 64, false, 2)                   \
+    X(SEQUENCE_IRRADIANCE_HORIZON_RGB, "sunsky_sequence_irradiance_horizon_rgb", 64, false, 2)     \
+    X(SEQUENCE_IRRADIANCE_HORIZON_SPEC, "sunsky_sequence_irradiance_horizon_spec", 64, false, 2)   \
     X(SEQUENCE_IRRADIANCE_VJP_NORMAL_RGB, "sunsky_sequence_irradiance_vjp_normal_rgb", 64, false, 2)   \
     X(SEQUENCE_IRRADIANCE_VJP_NORMAL_SPEC, "sunsky_sequence_irradiance_vjp_normal_spec", 64, false, 2) \
     X(SEQUENCE_IRRADIANCE_ADJOINT, "sunsky_sequence_irradiance_adjoint", kSeqIrrGradAdjointBlocksPerCu, false, 1) \
@@ -704,6 +706,10 @@ struct sunsky_sequence {
     std::vector<float> irr_sky, irr_flux;
     float* d_irr = nullptr;
     SeqIrradiance irr = {};
+    // the grid column j_k of every frame's sun (irradiance_horizon's sectors); on the device the
+    // columns of the image's suns, in the image's order, behind the image
+    std::vector<int> irr_sun_cols;
+    const int* d_irr_sun_cols = nullptr;
     LambdaSet irr_L = {};                    // the spectral planes' wavelengths (the weight gradient's sky terms)
     // gradients of the irradiance (prepare_irradiance_grad): asked for once (sticky: a later
     // prepare_irradiance restages it), staged for the current tables when irr_grad_ready
@@ -1173,9 +1179,9 @@ void seq_irradiance_host(const sunsky_sequence* q, int nz, int nphi, const Lambd
 
 // The image the hot path walks, from the tables: per cell c_ij.xyz and omega R_p[i, j], then per
 // frame with a non-zero w_k F_k (order kept) s_k.xyz and w_k F_k[p]; records of seq_irr_record
-// floats.  Returns the number of sun records.
+// floats.  Returns the number of sun records; kept: their frames.
 int seq_irradiance_image(const sunsky_sequence* q, int nz, int nphi, int planes, float omega, const std::vector<float>& sky,
-                         const std::vector<float>& flux, std::vector<float>& image) {
+                         const std::vector<float>& flux, std::vector<float>& image, std::vector<int>& kept) {
     const int rec = seq_irr_record(planes);
     const size_t cells = (size_t)nz * (size_t)nphi;
     image.assign((cells + (size_t)q->count) * rec, 0.f);
@@ -1198,10 +1204,25 @@ int seq_irradiance_image(const sunsky_sequence* q, int nz, int nphi, int planes,
         }
         if (!any) continue;
         r[0] = h->sun_n[0]; r[1] = h->sun_n[1]; r[2] = h->sun_n[2];
+        kept.push_back(k);
         ++nsuns;
     }
     image.resize((cells + (size_t)nsuns) * rec);
     return nsuns;
+}
+
+// The grid column of every frame's sun (sunsky_sequence_get_irradiance_sun_columns): the column
+// seq_sky_cell takes for a direction, with the host's atan2f.  A sun at the pole: column 0.
+std::vector<int> seq_irradiance_sun_columns(const sunsky_sequence* q, int nphi) {
+    std::vector<int> cols((size_t)q->count);
+    const float inv_dphi = (float)nphi / kTwoPi;
+    for (int k = 0; k < q->count; ++k) {
+        const SeqFrame<1>* h = seq_header(q, k);
+        float phi = atan2f(h->sun_n[1], h->sun_n[0]);
+        phi = phi < 0.f ? phi + kTwoPi : phi;
+        cols[(size_t)k] = std::min(std::max((int)(phi * inv_dphi), 0), nphi - 1);
+    }
+    return cols;
 }
 
 // The workspace bound of the irradiance gradients in floats: kSeqIrrGradWorkspaceFloats, or the
@@ -2445,7 +2466,9 @@ int sunsky_sequence_prepare_irradiance(sunsky_sequence* seq, int n_z, int n_phi,
         T.sin2_half_ap = 1.f / seq->kargs.inv_sin2_half_ap;
         const float omega = (float)(2.0 * 3.14159265358979323846 / (double)cells);
         std::vector<float> sky(cells * planes), flux((size_t)planes * count), image;
+        std::vector<int> cols = seq_irradiance_sun_columns(seq, n_phi);
         auto accept = [&] {
+            seq->irr_sun_cols = std::move(cols);
             seq->irr_sky = std::move(sky);
             seq->irr_flux = std::move(flux);
             seq->irr_omega = omega;
@@ -2470,7 +2493,8 @@ int sunsky_sequence_prepare_irradiance(sunsky_sequence* seq, int n_z, int n_phi,
         // more than planes, so it is never smaller
         const size_t rec = (size_t)seq_irr_record(planes);
         const size_t image_cap = (cells + (size_t)count) * rec;
-        hip_check(hipMalloc(&seq->d_irr, sizeof(float) * image_cap), "hipMalloc");
+        static_assert(sizeof(int) == sizeof(float), "the suns' columns lie behind the image");
+        hip_check(hipMalloc(&seq->d_irr, sizeof(float) * (image_cap + (size_t)count)), "hipMalloc");
         T.sky = seq->d_irr;
         T.flux = seq->d_irr + sky.size();
         const SunskyKArgs* K = seq->d_state;
@@ -2483,9 +2507,15 @@ int sunsky_sequence_prepare_irradiance(sunsky_sequence* seq, int n_z, int n_phi,
         hip_check(hipStreamSynchronize(nullptr), "hipStreamSynchronize");
         hip_check(hipMemcpy(sky.data(), T.sky, sizeof(float) * sky.size(), hipMemcpyDeviceToHost), "hipMemcpy");
         hip_check(hipMemcpy(flux.data(), T.flux, sizeof(float) * flux.size(), hipMemcpyDeviceToHost), "hipMemcpy");
-        const int nsuns = seq_irradiance_image(seq, n_z, n_phi, planes, omega, sky, flux, image);
+        std::vector<int> kept;
+        const int nsuns = seq_irradiance_image(seq, n_z, n_phi, planes, omega, sky, flux, image, kept);
         hip_check(hipMemcpy(seq->d_irr, image.data(), sizeof(float) * image.size(), hipMemcpyHostToDevice), "hipMemcpy");
         seq->irr = SeqIrradiance{seq->d_irr, seq->d_irr + cells * rec, n_z, n_phi, nsuns, planes};
+        for (int& k : kept) k = cols[(size_t)k];   // the image's suns' columns, in its order
+        seq->d_irr_sun_cols = reinterpret_cast<const int*>(seq->d_irr + image_cap);
+        if (nsuns)
+            hip_check(hipMemcpy(seq->d_irr + image_cap, kept.data(), sizeof(int) * kept.size(), hipMemcpyHostToDevice),
+                      "hipMemcpy");
         accept();
     });
 }
@@ -2534,6 +2564,45 @@ int sunsky_sequence_irradiance(const sunsky_sequence* seq, sunsky_vec3_in nrm, c
         run_kernel(seq->mod, seq->xform_form(), seq->precision,
                    seq->variant == kSpectral ? K_SEQUENCE_IRRADIANCE_SPEC : K_SEQUENCE_IRRADIANCE_RGB, n, args,
                    (hipStream_t)stream);
+    });
+}
+
+int sunsky_sequence_get_irradiance_sun_columns(const sunsky_sequence* seq, int* out, size_t cap, size_t* count) {
+    if (!seq) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sequence");
+    return guarded([&] {
+        seq->require_irradiance();
+        const std::vector<int>& c = seq->irr_sun_cols;
+        if (count) *count = c.size();
+        if (out) std::memcpy(out, c.data(), sizeof(int) * std::min(cap, c.size()));
+    });
+}
+
+int sunsky_sequence_irradiance_horizon(const sunsky_sequence* seq, sunsky_vec3_in nrm, const float* horizon, int n_sectors,
+                                       size_t n_profiles, size_t hstride, const uint8_t* active, size_t n, float* out,
+                                       size_t ostride, void* stream) {
+    SUNSKY_PHASE("EndpointEvaluate", "sequence_irradiance_horizon");
+    if (!seq) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sequence");
+    if (n == 0) return SUNSKY_OK;
+    if (!nrm.x || !nrm.y || !nrm.z || !out) return fail(SUNSKY_ERROR_INVALID_VALUE, "null normal / output pointer");
+    if (!horizon) return fail(SUNSKY_ERROR_INVALID_VALUE, "null horizon pointer");
+    if (n > 0xffffffffull) return fail(SUNSKY_ERROR_INVALID_VALUE, "more than 2^32 receivers");
+    return guarded([&] {
+        seq->require_irradiance();   // first: the message names the missing call on any sequence
+        if (n_sectors < 1 || seq->irr_nphi % n_sectors != 0)
+            throw std::invalid_argument("n_sectors must be >= 1 and divide the irradiance tables' n_phi");
+        if (n_profiles != 1 && n_profiles != n) throw std::invalid_argument("n_profiles must be 1 or n");
+        if (n_profiles == n && n_sectors > 1 && hstride < n) throw std::invalid_argument("horizon_stride < n");
+        if (seq->irr_planes > 1 && ostride < n) throw std::invalid_argument("out_stride < n");
+        seq->require_device();
+        DeviceScope g(seq->device);
+        const SunskyKArgs* K = seq->d_state;
+        SeqIrradiance S = seq->irr;
+        SeqIrrHorizon Z = {horizon, seq->d_irr_sun_cols, hstride, n_sectors, seq->irr_nphi / n_sectors,
+                           n_profiles == 1 ? 0 : 1, 0};
+        void* args[] = {&K, &S, &Z, (void*)&nrm.x, (void*)&nrm.y, (void*)&nrm.z, &active, &n, &out, &ostride};
+        run_kernel(seq->mod, seq->xform_form(), seq->precision,
+                   seq->variant == kSpectral ? K_SEQUENCE_IRRADIANCE_HORIZON_SPEC : K_SEQUENCE_IRRADIANCE_HORIZON_RGB, n,
+                   args, (hipStream_t)stream);
     });
 }
 

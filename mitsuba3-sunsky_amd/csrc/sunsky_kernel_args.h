@@ -270,6 +270,18 @@ struct SeqIrradiance {
 };
 static_assert(sizeof(SeqIrradiance) == 32 && offsetof(SeqIrradiance, nz) == 16, "SeqIrradiance layout");
 
+// sunsky_sequence_irradiance_horizon: the horizon profiles beside the image.  Sector b's plane
+// starts at h + b * stride; receiver r reads element r * per_receiver of it (0: one shared profile).
+struct SeqIrrHorizon {
+    const float* h;            // [sectors] planes of sin(horizon elevation)
+    const int* sun_cols;       // [nsuns] column j_k of the image's suns, in the image's order
+    size_t stride;             // floats between two sectors' planes
+    int sectors, sector_len;   // sector_len = nphi / sectors columns each
+    int per_receiver;          // 1: element r of a plane is receiver r's; 0: element 0 is everyone's
+    int pad;
+};
+static_assert(sizeof(SeqIrrHorizon) == 40 && offsetof(SeqIrrHorizon, sectors) == 24, "SeqIrrHorizon layout");
+
 // ---------------------------------------------------------------- gradients of the sequence irradiance
 // sunsky_sequence_prepare_irradiance_grad / sunsky_sequence_irradiance_vjp (sunsky_amd.h has the
 // definition).  The weight gradient goes through the adjoint image: per slice of receivers one

@@ -5636,9 +5636,18 @@ __device__ __forceinline__ seq_f2 seq_fma2(seq_f2 a, float b, seq_f2 c) {
 // The order is the contract: a row's cells in column order into a row sum that starts at 0,
 // the row sums in row order into the plane's sum, then the suns in list order, every
 // product-and-add one fma; the two receivers of a lane never meet.
-template <int NP, int REC>
+//
+// HZ (sunsky_sequence_irradiance_horizon): the column loop is cut into the profile's
+// sectors (their length is wave-uniform).  Per row and sector the lane's two h values, loaded one
+// sector ahead of their use, give v = clamp(fma(-h, n_z, i + 1), 0, 1) once; per cell one packed
+// multiply (the clamped cosine times v) sits beside the forward's instructions.  A sun counts
+// when s_k.z >= h of its column's sector.  h: elements e0 and e1 of the sector's plane in global
+// memory (coalesced over receivers; one address for a shared profile), read again in every row
+// and served by the caches (a copy per lane in LDS was measured and lost: DESIGN.md).
+template <int NP, int REC, bool HZ = false>
 __device__ __forceinline__ void seq_irr_pass(const SeqIrradiance& S, int rec, int p0, seq_f2 nx, seq_f2 ny, seq_f2 nz,
-                                             seq_f2 (&acc)[NP]) {
+                                             seq_f2 (&acc)[NP], const SeqIrrHorizon* Z = nullptr, size_t e0 = 0,
+                                             size_t e1 = 0) {
     if constexpr (REC != 0) rec = REC;
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wold-style-cast"
@@ -5653,6 +5662,54 @@ __device__ __forceinline__ void seq_irr_pass(const SeqIrradiance& S, int rec, in
     };
 #pragma unroll
     for (int p = 0; p < NP; ++p) acc[p] = zero;
+    if constexpr (HZ) {
+        const seq_f2 one = {1.f, 1.f}, fnz = {(float)S.nz, (float)S.nz};
+        const int sectors = Z->sectors, len = Z->sector_len;
+        // the lane's two h values of sector b
+        auto profile = [&](int b) {
+            const float* q = Z->h + (size_t)b * Z->stride;
+            const seq_f2 h = {q[e0], q[e1]};
+            return h;
+        };
+#pragma unroll 1
+        for (int i = 0; i < S.nz; ++i) {
+            seq_f2 row[NP];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) row[p] = zero;
+            const seq_f2 top = {(float)(i + 1), (float)(i + 1)};
+            seq_f2 h = profile(0);
+#pragma unroll 1
+            for (int b = 0; b < sectors; ++b) {
+                const seq_f2 next = profile(b + 1 < sectors ? b + 1 : 0);
+                const seq_f2 v = __builtin_elementwise_min(
+                    __builtin_elementwise_max(__builtin_elementwise_fma(-h, fnz, top), zero), one);
+#pragma unroll 4
+                for (int j = 0; j < len; ++j, r += rec) {
+                    const seq_f2 c = cosine(r) * v;
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) row[p] = seq_fma2(c, r[p], row[p]);
+                }
+                h = next;
+            }
+#pragma unroll
+            for (int p = 0; p < NP; ++p) acc[p] += row[p];
+        }
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wold-style-cast"
+        seq_cint_p cols = (seq_cint_p)Z->sun_cols;
+#pragma clang diagnostic pop
+#pragma unroll 1
+        for (int k = 0; k < S.nsuns; ++k, u += rec) {
+            const seq_f2 h = profile(cols[k] / len);
+            const float sz = u[-1 - p0];
+            seq_f2 c = cosine(u);
+            c[0] = sz >= h[0] ? c[0] : 0.f;
+            c[1] = sz >= h[1] ? c[1] : 0.f;
+#pragma unroll
+            for (int p = 0; p < NP; ++p) acc[p] = seq_fma2(c, u[p], acc[p]);
+        }
+        return;
+    }
 #pragma unroll 1
     for (int i = 0; i < S.nz; ++i) {
         seq_f2 row[NP];
@@ -5678,10 +5735,13 @@ __device__ __forceinline__ void seq_irr_pass(const SeqIrradiance& S, int rec, in
 // Two receivers per lane, t and t + ceil(n / 2) (both streams coalesced), grid-stride over the
 // pairs.  RGB: one pass of 3 planes over 32-byte records.  Spectral: passes of 8, 4, 2 and 1
 // planes (a plane's sum does not depend on the pass it is in).
-template <bool RGB>
+// HZ: under the horizon profiles Z; a lane's elements of a sector's plane are its receivers'
+// indices (the first one's for a missing second receiver), or 0 for a shared profile.
+template <bool RGB, bool HZ = false>
 __device__ __forceinline__ void seq_irradiance_body(const SunskyKArgs& K, const SeqIrradiance& S, const float* nx,
                                                     const float* ny, const float* nz, const uint8_t* active, size_t n,
-                                                    float* __restrict__ out, size_t ostride) {
+                                                    float* __restrict__ out, size_t ostride,
+                                                    const SeqIrrHorizon* Z = nullptr) {
     const size_t stride = (size_t)gridDim.x * blockDim.x, pairs = (n + 1) / 2;
     for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < pairs; t += stride) {
         const size_t idx[2] = {t, t + pairs};
@@ -5699,9 +5759,14 @@ __device__ __forceinline__ void seq_irradiance_body(const SunskyKArgs& K, const 
             store_nt(m[0] ? v[0] : 0.f, out + (size_t)p * ostride + idx[0]);
             if (has[1]) store_nt(m[1] ? v[1] : 0.f, out + (size_t)p * ostride + idx[1]);
         };
+        size_t e0 = 0, e1 = 0;
+        if constexpr (HZ) {
+            e0 = Z->per_receiver ? idx[0] : 0;
+            e1 = Z->per_receiver ? (has[1] ? idx[1] : idx[0]) : 0;
+        }
         if constexpr (RGB) {
             seq_f2 acc[3];
-            seq_irr_pass<3, seq_irr_record(3)>(S, 0, 0, lx, ly, lz, acc);
+            seq_irr_pass<3, seq_irr_record(3), HZ>(S, 0, 0, lx, ly, lz, acc, Z, e0, e1);
 #pragma unroll
             for (int p = 0; p < 3; ++p) store(p, acc[p]);
         } else {
@@ -5710,7 +5775,7 @@ __device__ __forceinline__ void seq_irradiance_body(const SunskyKArgs& K, const 
             auto pass = [&](auto np) {
                 constexpr int NP = decltype(np)::value;
                 seq_f2 acc[NP];
-                seq_irr_pass<NP, 0>(S, rec, p0, lx, ly, lz, acc);
+                seq_irr_pass<NP, 0, HZ>(S, rec, p0, lx, ly, lz, acc, Z, e0, e1);
 #pragma unroll
                 for (int p = 0; p < NP; ++p) store(p0 + p, acc[p]);
                 p0 += NP;
@@ -5738,6 +5803,21 @@ __device__ __forceinline__ void seq_irradiance_body(const SunskyKArgs& K, const 
     }
 SS_SEQUENCE_IRRADIANCE(_fast)
 SS_SEQUENCE_IRRADIANCE(_ref)
+
+// The same under a per-receiver (or one shared) horizon profile: sunsky_sequence_irradiance_horizon
+#define SS_SEQUENCE_IRRADIANCE_HORIZON(SUFFIX)                                                                 \
+    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_irradiance_horizon_rgb##SUFFIX(     \
+        const SunskyKArgs* __restrict__ Kp, SeqIrradiance S, SeqIrrHorizon Z, const float* nx, const float* ny, \
+        const float* nz, const uint8_t* active, size_t n, float* out, size_t ostride) {                        \
+        seq_irradiance_body<true, true>(*Kp, S, nx, ny, nz, active, n, out, ostride, &Z);                      \
+    }                                                                                                          \
+    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_irradiance_horizon_spec##SUFFIX(    \
+        const SunskyKArgs* __restrict__ Kp, SeqIrradiance S, SeqIrrHorizon Z, const float* nx, const float* ny, \
+        const float* nz, const uint8_t* active, size_t n, float* out, size_t ostride) {                        \
+        seq_irradiance_body<false, true>(*Kp, S, nx, ny, nz, active, n, out, ostride, &Z);                     \
+    }
+SS_SEQUENCE_IRRADIANCE_HORIZON(_fast)
+SS_SEQUENCE_IRRADIANCE_HORIZON(_ref)
 
 // ======================================================================
 // Gradients of the irradiance (sunsky_sequence_irradiance_vjp; the definition is in sunsky_amd.h).

@@ -150,6 +150,9 @@ _SIGS = {
     "sunsky_sequence_irradiance_info": (C.c_int, [vp, C.POINTER(SequenceIrradianceDesc)]),
     "sunsky_sequence_get_irradiance_table": (C.c_int, [vp, C.c_int, c_float_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sunsky_sequence_irradiance": (C.c_int, [vp, Vec3In, vp, C.c_size_t, vp, C.c_size_t, vp]),
+    "sunsky_sequence_get_irradiance_sun_columns": (C.c_int, [vp, C.POINTER(C.c_int), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "sunsky_sequence_irradiance_horizon": (C.c_int, [vp, Vec3In, vp, C.c_int, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp,
+                                                     C.c_size_t, vp]),
     "sunsky_sequence_prepare_irradiance_grad": (C.c_int, [vp]),
     "sunsky_sequence_irradiance_vjp": (C.c_int, [vp, Vec3In, vp, C.c_size_t, vp, C.c_size_t, Vec3Out, vp, vp]),
     "sunsky_direct_diffuse": (C.c_int, [vp, Vec3In, vp, vp, C.c_int, C.c_size_t, C.c_uint32, C.c_uint32,

@@ -25,6 +25,14 @@ def sun_coordinates(year, month, day, hour, minute=0.0, second=0.0, latitude=35.
     return np.array(out, dtype=np.float32)
 
 
+def horizon_from_elevation(degrees):
+    """sin of horizon elevation angles in degrees as fp32, the unit of SunskySequence.irradiance's
+    `horizon`: a tensor stays a tensor (on its device), anything else becomes a numpy array."""
+    if isinstance(degrees, torch.Tensor):
+        return torch.sin(torch.deg2rad(degrees.to(torch.float64))).to(torch.float32)
+    return np.sin(np.deg2rad(np.asarray(degrees, dtype=np.float64))).astype(np.float32)
+
+
 def _time_fields(t):
     if isinstance(t, datetime.datetime):
         return t.year, t.month, t.day, float(t.hour), float(t.minute), t.second + t.microsecond * 1e-6
@@ -307,19 +315,59 @@ class SunskySequence:
         i = self.irradiance_info()
         return a.reshape(i["n_planes"], i["n_z"], i["n_phi"]) if name == "sky" else a.reshape(i["n_planes"], -1)
 
-    def irradiance(self, normals, active=None, out=None):
+    def irradiance_sun_columns(self):
+        """The grid column j_k of every frame's sun as int32 (K,): what picks a sun's sector of a
+        horizon profile (sunsky_sequence_get_irradiance_sun_columns).  Needs prepare_irradiance."""
+        cnt = C.c_size_t()
+        check(lib().sunsky_sequence_get_irradiance_sun_columns(self._h, None, 0, C.byref(cnt)))
+        buf = (C.c_int * cnt.value)()
+        check(lib().sunsky_sequence_get_irradiance_sun_columns(self._h, buf, cnt.value, C.byref(cnt)))
+        return np.array(buf, dtype=np.int32)
+
+    def _horizon(self, horizon, n):
+        """A horizon argument checked against n receivers and the prepared grid: the tensor the
+        library reads, then (H, n_profiles, stride between two sectors' planes)."""
+        if not isinstance(horizon, torch.Tensor) or horizon.dtype != torch.float32:
+            raise ValueError("horizon must be a float32 tensor of shape (H,), (H, 1) or (H, n)")
+        if horizon.dim() not in (1, 2) or horizon.shape[0] < 1 or (horizon.dim() == 2 and horizon.shape[1] not in (1, n)):
+            raise ValueError(f"horizon must have shape (H,), (H, 1) or (H, {n}), got {tuple(horizon.shape)}")
+        sectors, n_phi = horizon.shape[0], self.irradiance_info()["n_phi"]
+        if n_phi % sectors:
+            raise ValueError(f"the horizon's {sectors} sectors do not divide the irradiance tables' n_phi = {n_phi}")
+        if self.device is not None and horizon.device != self.device:
+            raise ValueError(f"horizon must be on {self.device}")
+        per_receiver = horizon.dim() == 2 and horizon.shape[1] == n and n > 1
+        if per_receiver and (horizon.stride(1) != 1 or sectors > 1 and horizon.stride(0) < n):
+            horizon = horizon.contiguous()   # rows must be contiguous; a row stride is passed on as it is
+        return horizon, sectors, n if per_receiver else 1, horizon.stride(0)
+
+    def irradiance(self, normals, active=None, out=None, horizon=None):
         """E_p(n) of the cumulative sky and suns on receivers with world-space normals (3, n) ->
         (P, n): the fixed quadrature of sunsky_sequence_irradiance over the prepared tables.
-        Needs prepare_irradiance; `out` may have a row stride, as eval's."""
+        Needs prepare_irradiance; `out` may have a row stride, as eval's.
+
+        horizon: far shading (sunsky_sequence_irradiance_horizon).  A float32 tensor of
+        sin(horizon elevation) per azimuth sector of the emitter's local frame (see
+        horizon_from_elevation), (H,) or (H, 1) for one profile shared by all receivers, (H, n)
+        for one per receiver; H divides the tables' n_phi.  A sector hides the share of each sky
+        cell below its horizon and every sun below it.  None: the unoccluded call, unchanged."""
         if self.device is None:
             self.irradiance_info()   # an unprepared sequence says so first
+            if horizon is not None:
+                self._horizon(horizon, int(np.shape(normals)[-1]))
             raise ValueError("host-only sequence (over a host-only emitter) cannot launch kernels")
         nrm, vin = SunskyEmitter._vec_in(self, normals)
         n = nrm.shape[1]
         planes = self.irradiance_info()["n_planes"]
+        if horizon is not None:
+            horizon, sectors, profiles, hstride = self._horizon(horizon, n)
         out = SunskyEmitter._out(self, out, (planes, n), row_stride_ok=True)
         mask = SunskyEmitter._mask(self, active, n)
-        check(lib().sunsky_sequence_irradiance(self._h, vin, _ptr(mask), n, _ptr(out), out.stride(0), self._stream()))
+        if horizon is None:
+            check(lib().sunsky_sequence_irradiance(self._h, vin, _ptr(mask), n, _ptr(out), out.stride(0), self._stream()))
+        else:
+            check(lib().sunsky_sequence_irradiance_horizon(self._h, vin, _ptr(horizon), sectors, profiles, hstride,
+                                                           _ptr(mask), n, _ptr(out), out.stride(0), self._stream()))
         return out
 
     # ------------------------------------------------------------ gradients and updates

@@ -16,7 +16,10 @@ does an eval's transcendental work with no HBM traffic).  Not part of bench.py.
   --irradiance -- instead: sequence.irradiance on 2^20 receivers beside the chunked torch
                 formulation a user writes from the read-back tables (see irradiance()).
   --irradiance-grad -- instead: sequence.irradiance_vjp beside sequence.irradiance and the torch
-                formulations of both gradients (see irradiance_grad())."""
+                formulations of both gradients (see irradiance_grad()).
+  --irradiance-horizon -- instead: sequence.irradiance under a shared and a per-receiver horizon
+                profile beside the unoccluded call and the masked chunked torch formulation
+                (see irradiance_horizon())."""
 import json
 import os
 import statistics
@@ -219,6 +222,76 @@ def irradiance(ks, dev):
     print("sequence_bench irradiance done")
 
 
+def irradiance_horizon(ks, dev):
+    """--irradiance-horizon: irradiance()'s workload (n = 2^20 normals on the sphere, RGB, 64 x 256
+    cells) under horizon profiles of H = 32 sectors, one shared and one per receiver (sin of the
+    elevation uniform in [0, 0.5]).  Two yardsticks of the same session: (a) sequence.irradiance at
+    the same n, the ratio the extra multiply per cell and the profile loads cost; (b) what a user
+    writes today from the tables read back once -- irradiance()'s chunked torch formulation with
+    the visible share v (an n x cells mask per chunk) and the suns' visibility multiplied in.
+    Prints the medians, both ratios and the largest difference of the two results."""
+    n, chunk, sectors = 1 << 20, 1 << 14, 32
+    g = torch.Generator(device=dev).manual_seed(3)
+    v = torch.randn((3, n), device=dev, generator=g)
+    nrm = (v / v.norm(dim=0, keepdim=True)).contiguous()
+    h_per = (0.5 * torch.rand((sectors, n), device=dev, generator=g)).contiguous()
+    h_shared = h_per[:, 0].contiguous()
+    base = {"type": "sunsky", "sun_direction": [0.3, 0.4, 0.866], "turbidity": 3.0, "albedo": 0.2}
+    for k in ks:
+        dirs, turb, wts = frames(k)
+        seq = ss.SunskySequence(ss.load_dict(dict(base)), dirs, turb, wts)
+        seq.prepare_irradiance()
+        info = seq.irradiance_info()
+        nz, nphi = info["n_z"], info["n_phi"]
+        length = nphi // sectors
+        z = (np.arange(nz) + 0.5) / nz
+        phi = (np.arange(nphi) + 0.5) * (2 * np.pi / nphi)
+        st = np.sqrt(1 - z * z)
+        D = np.stack([np.outer(st, np.cos(phi)).ravel(), np.outer(st, np.sin(phi)).ravel(), np.repeat(z, nphi)], 1)
+        D_t = torch.from_numpy(D.astype(np.float32)).to(dev)                                        # (cells, 3)
+        R_t = torch.from_numpy(info["omega"] * seq.irradiance_table("sky").reshape(3, -1)).to(dev)   # (3, cells)
+        S_t = torch.from_numpy(np.stack([seq.frame(i)["sun_dir_local"] for i in range(k)])).to(dev)  # (K, 3)
+        F_t = torch.from_numpy(wts[None, :] * seq.irradiance_table("sun_flux")).to(dev)              # (3, K)
+        sun_sector = torch.from_numpy(seq.irradiance_sun_columns().astype(np.int64) // length).to(dev)   # (K,)
+        top = torch.arange(1, nz + 1, device=dev, dtype=torch.float32)
+        out_t = torch.empty((3, n), device=dev)
+        out = torch.empty((3, n), device=dev)
+        out_s = torch.empty((3, n), device=dev)
+        out_0 = torch.empty((3, n), device=dev)
+
+        def torch_chunks(h):
+            for a in range(0, n, chunk):
+                nl = nrm[:, a:a + chunk].t()
+                hc = (h[:, a:a + chunk] if h.dim() == 2 else h[:, None].expand(sectors, nl.shape[0])).t()   # (c, H)
+                vis = (top[None, :, None] - hc[:, None, :] * nz).clamp_(0, 1)                                # (c, nz, H)
+                vis = vis.repeat_interleave(length, dim=2).reshape(nl.shape[0], -1)                          # (c, cells)
+                seen = S_t[None, :, 2] >= hc[:, sun_sector]                                                  # (c, K)
+                e = (torch.relu(nl @ D_t.t()) * vis) @ R_t.t() + (torch.relu(nl @ S_t.t()) * seen) @ F_t.t()
+                out_t[:, a:a + chunk] = e.t()
+
+        t_plain, all_plain = median_ms(lambda: seq.irradiance(nrm, out=out_0))
+        t_per, all_per = median_ms(lambda: seq.irradiance(nrm, out=out, horizon=h_per))
+        t_shared, all_shared = median_ms(lambda: seq.irradiance(nrm, out=out_s, horizon=h_shared))
+        t_torch, all_torch = median_ms(lambda: torch_chunks(h_per))
+        diff = float(((out - out_t).abs().max() / out_t.abs().max()).item())
+        torch_chunks(h_shared)
+        torch.cuda.synchronize()
+        diff_s = float(((out_s - out_t).abs().max() / out_t.abs().max()).item())
+        print(json.dumps({"K": k, "n": n, "table": [nz, nphi], "sectors": sectors,
+                          "irradiance_ms": round(t_plain, 3), "horizon_per_receiver_ms": round(t_per, 3),
+                          "horizon_shared_ms": round(t_shared, 3), "torch_masked_chunked_ms": round(t_torch, 3),
+                          "per_receiver_over_irradiance": round(t_per / t_plain, 3),
+                          "shared_over_irradiance": round(t_shared / t_plain, 3),
+                          "torch_over_per_receiver": round(t_torch / t_per, 2),
+                          "occluded_share_of_E": round(float((1 - out.sum() / out_0.sum()).item()), 4),
+                          "max_diff_vs_torch_of_max": diff, "max_diff_vs_torch_of_max_shared": diff_s,
+                          "irradiance_ms_all": [round(t, 3) for t in all_plain],
+                          "horizon_per_receiver_ms_all": [round(t, 3) for t in all_per],
+                          "horizon_shared_ms_all": [round(t, 3) for t in all_shared],
+                          "torch_masked_chunked_ms_all": [round(t, 3) for t in all_torch]}), flush=True)
+    print("sequence_bench irradiance-horizon done")
+
+
 def irradiance_grad(ks, dev):
     """--irradiance-grad: sequence.irradiance_vjp on irradiance()'s workload (n = 2^20 normals on the
     sphere, RGB, 64 x 256 cells) with a standard-normal cotangent: the normal gradient alone, the
@@ -317,7 +390,7 @@ def irradiance_grad(ks, dev):
 
 
 def main():
-    flags = ("--sampling", "--grad", "--no-loop", "--irradiance", "--irradiance-grad")
+    flags = ("--sampling", "--grad", "--no-loop", "--irradiance", "--irradiance-grad", "--irradiance-horizon")
     args = [a for a in sys.argv[1:] if a not in flags]
     ks = [int(a) for a in args] or [24, 365]
     dev = torch.device("cuda", 0)
@@ -328,6 +401,8 @@ def main():
         return irradiance(ks, dev)
     if "--irradiance-grad" in sys.argv[1:]:
         return irradiance_grad(ks, dev)
+    if "--irradiance-horizon" in sys.argv[1:]:
+        return irradiance_horizon(ks, dev)
     if "--grad" in sys.argv[1:]:
         return grad(ks, dev, "--no-loop" not in sys.argv[1:])
     g = torch.Generator(device=dev).manual_seed(3)
