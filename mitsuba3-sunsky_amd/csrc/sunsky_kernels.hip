@@ -350,12 +350,15 @@ __device__ __forceinline__ void add_sun_terms(const SunskyKArgs& K, DirTerms& t)
             t.sun_pos = pos;
             t.sun_x = elevation - kHalfPi * (frac * frac * frac);
             // cos^2 psi = 1 - sin^2(gamma) / sin^2(half aperture) cancels towards the limb, where
-            // d cos psi / d gamma is unbounded: its inputs in fp64.  With v = wo - n (exact in
-            // fp32 next to the sun, the reference's subtraction) and |v|^2 = 4 h^2,
-            // sin^2(gamma) = sin^2(2 asin h) = |v|^2 (1 - |v|^2 / 4); the fp32 products widen
-            // exactly.  One rounding to fp32 before the square root (relative 3e-8 on cos psi).
-            const double vx = (double)(t.wx - K.sun_n[0]), vy = (double)(t.wy - K.sun_n[1]),
-                         vz = (double)(t.cos_theta - K.sun_n[2]);
+            // d cos psi / d gamma is unbounded: its inputs in fp64.  With the chord v = wo - n
+            // formed in fp64, exactly as sun_disc64 does, and |v|^2 = 4 h^2,
+            // sin^2(gamma) = sin^2(2 asin h) = |v|^2 (1 - |v|^2 / 4).  (The fp32 subtraction is
+            // exact only next to the sun: at the limb of a 12 deg disc its rounding moved the
+            // sampling weights by up to 1.3e-4, 11.7 x the bound of
+            // tests/test_gpu_sampler_disc_literal.py, and a 5 deg disc at 3 deg by 2.3e-5.)
+            // One rounding to fp32 before the square root (relative 3e-8 on cos psi).
+            const double vx = (double)t.wx - (double)K.sun_n[0], vy = (double)t.wy - (double)K.sun_n[1],
+                         vz = (double)t.cos_theta - (double)K.sun_n[2];
             const double v2 = fma(vz, vz, fma(vy, vy, vx * vx));
             const double inv = (double)K.cpsi_inv_hi + (double)K.cpsi_inv_lo;
             const float c2 = (float)fma(-inv, v2 * fma(-0.25, v2, 1.0), 1.0);
@@ -394,7 +397,9 @@ __device__ __forceinline__ const SunskyKArgs& opaque_kargs(const SunskyKArgs& K)
 // there is off by up to 4.9e-5 (the reference's own fp32 by 1.5e-4); this branch holds the
 // literal 1e-5 against the fp64 evaluation of the staged fp32 state
 // (tests/test_gpu_disc_literal.py).  The samplers keep the
-// fp32 form (65 % of their lanes are sun picks, already within 1e-5 of fp64).
+// fp32 form (65 % of their lanes are sun picks): add_sun_terms<true> with cos psi from the fp64
+// chord, held to the forward bound of the fp32 Horner forms against the same fp64 value
+// (tests/test_gpu_sampler_disc_literal.py).
 struct SunDisc64 {
     int pos;     // render_sun's segment: the reference's fp32 decision (sun_segment_index)
     double x;    // elevation - pi/2 (pos / 45)^3: the fp32 elevation (elevation_fast, 0.7 ulp;
