@@ -1,15 +1,18 @@
-"""More than one grid-stride step per lane.  Every batch kernel is a grid-stride loop over a
-grid capped at a number of workgroups per CU; at the default caps only a batch beyond ~16.8M
-directions makes a lane take a second step, so no other test walks a kernel's loop twice, nor
-takes the 11-node broadcast kernel with its dynamic-LDS occupancy cap (which engages only
-then).  A child process with SUNSKY_AMD_BLOCKS_PER_CU=1 (one workgroup per CU) runs a batch of
-~655k directions, one in eight of them inside the sun disc (the disc lanes' second pass of the
-broadcast kernels).  eval, eval_direction, pdf_direction and eval_spectral_broadcast get
-16-byte-aligned planes through the C ABI (gpu_grid_stride_worker.py), so each call is a
+"""More than one grid-stride step per lane.  Every batch kernel is a grid-stride loop over a grid
+capped at a number of workgroups per CU; at the default caps only a batch beyond ~16.8M
+directions makes a lane take a second step, so no other test walks these kernels' loops twice,
+nor takes the 11-node broadcast kernel with its dynamic-LDS occupancy cap (which engages only
+then).  (The worker leaves out the six direct-lighting kernels, sunsky_sample_wavelengths_{rgb,
+spec} and sunsky_bake_latlong_{rgb,spec}: tests/test_gpu_direct_shapes.py walks their loops two
+to three times in the same way, with gpu_direct_worker.py; the sequence kernels have capped-grid
+tests of their own.) A child process with SUNSKY_AMD_BLOCKS_PER_CU=1 (one workgroup per CU) runs
+a batch of ~655k directions, one in eight of them inside the sun disc (the disc lanes' second
+pass of the broadcast kernels).  eval, eval_direction, pdf_direction and eval_spectral_broadcast
+get 16-byte-aligned planes through the C ABI (gpu_grid_stride_worker.py), so each call is a
 4-directions-per-lane body of two to three steps per lane and a 3-element scalar tail; the
-sampling kernels take 3 to 10 steps.  This process makes the same calls at the default grid
-(one step per lane).  Every output must be the same bit for bit: what a direction computes
-does not depend on the grid.
+sampling kernels take 3 to 10 steps.  This process makes the same calls at the default grid (one
+step per lane).  Every output must be the same bit for bit: what a direction computes does not
+depend on the grid.
 
 The grid itself cannot be observed from here: the test relies on the override being honoured
 (it is read in one place, grid_for of csrc/sunsky_capi.cpp, once per process)."""
