@@ -232,6 +232,8 @@ class Oracle:
         if self.spectral:
             lam = _f(np.asarray(wavelengths, dtype=np.float32).reshape(-1, n))
             k = lam.shape[0]
+            if not 1 <= k <= 16:   # the C side's per-sample buffer (kMaxLambdaPerRay)
+                raise ValueError(f"1..16 wavelengths per sample, got {k}")
         else:
             lam, k = None, 3
         w = np.zeros((k, n), dtype=self.dtype)

@@ -844,7 +844,7 @@ void N_(oracle_sample_direction)(const O_T *o, const float *ux, const float *uy,
         if (dist) dist[i] = 2 * radius;
         /* eval(si{wi = -d}) / pdf, masked by active, zeroed if non-finite */
         V3 wo = N_(xform_vec)(o->to_local, d);
-        R e[11];
+        R e[16]; /* up to 16 wavelengths per sample (kMaxLambdaPerRay), one entry each */
         if (!o->spectral)
             N_(eval_local)(o, wo, 0, e);
         else
