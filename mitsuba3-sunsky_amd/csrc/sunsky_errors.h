@@ -12,7 +12,7 @@
 namespace sunsky {
 namespace capi {
 
-std::string& last_error();   // thread-local, sunsky_capi.cpp
+std::string& last_error();   // thread-local, sunsky_launch.cpp
 
 inline int fail(int code, const std::string& msg) {
     last_error() = msg;

@@ -8,7 +8,7 @@ A. forward mode per lane: tiny and empty batches, 1 / 3 / 4 / 16 wavelength plan
 C. reverse mode at every shape of its two reductions: a ragged last workgroup, idle waves,
    sunsky_grad_reduce's unrolled loop (16 loads in flight while b + 240 < nblocks) with its
    hand-off to the remainder loop, and a batch beyond the VJP's own grid of
-   min(ceil(n / 256), 6 x CUs) workgroups (sunsky_eval_vjp, csrc/sunsky_capi.cpp), where some
+   min(ceil(n / 256), 6 x CUs) workgroups (sunsky_eval_vjp, csrc/sunsky_launch.h), where some
    lanes take a second grid-stride step; each against the JVP prefix sums, and bit for bit
    with a cotangent on one lane only, which no bar can hide a lost workgroup behind;
 D. reverse mode with a mask and at the wavelength edges;

@@ -60,7 +60,7 @@ def c3_dict(**kw):
 @pytest.mark.parametrize("precision", PRECISIONS)
 def test_c3_node_kernel_against_oracle(precision):
     """sunsky_eval_spec_nodes_v4_{fast,ref}: chosen by sunsky_eval_spectral_broadcast when
-    the list is exactly 320:40:720 (sunsky_capi.cpp); a ragged tail takes the VEC=1
+    the list is exactly 320:40:720 (sunsky_capi_emitter.cpp); a ragged tail takes the VEC=1
     broadcast kernel.  Sky lanes at 1e-5 of fp32, sun-disc lanes at the fp64 bar."""
     d = c3_dict()
     em = ss.SunskyEmitter(d, "spectral", precision=precision)

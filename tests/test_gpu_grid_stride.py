@@ -15,7 +15,7 @@ step per lane).  Every output must be the same bit for bit: what a direction com
 depend on the grid.
 
 The grid itself cannot be observed from here: the test relies on the override being honoured
-(it is read in one place, grid_for of csrc/sunsky_capi.cpp, once per process)."""
+(it is read in one place, grid_for of csrc/sunsky_launch.cpp, once per process)."""
 import os
 import subprocess
 import sys
