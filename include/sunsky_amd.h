@@ -20,7 +20,8 @@
  *     sample_ray, sample_wavelengths, direct_diffuse, direct_diffuse_rays,
  *     eval_jvp_dir, eval_vjp_dir, sequence_eval, sequence_sample_direction,
  *     sequence_pdf_direction, sequence_eval_vjp, sequence_irradiance,
- *     sequence_irradiance_horizon, sequence_irradiance_vjp)
+ *     sequence_irradiance_horizon, sequence_irradiance_vjp,
+ *     sequence_irradiance_series)
  *     allocate nothing, make no host-synchronous call and may be captured into
  *     a hipGraph (tests/test_graph_capture.py).  Kernels read the emitter state
  *     from device memory, which parameters_changed_async rewrites in place on
@@ -55,8 +56,9 @@ extern "C" {
                                         eval_jvp_dir, eval_vjp_dir; sun_coordinates and the
                                         sunsky_sequence_* calls (frame sequences, their
                                         sampling, update, gradients, irradiance, the
-                                        irradiance's gradients and the irradiance under a
-                                        horizon profile included) */
+                                        irradiance's gradients, the irradiance under a
+                                        horizon profile and the per-frame irradiance
+                                        series included) */
 
 typedef enum sunsky_status {
     SUNSKY_OK = 0,
@@ -585,6 +587,72 @@ int sunsky_sequence_get_irradiance_sun_columns(const sunsky_sequence *seq, int *
 int sunsky_sequence_irradiance_horizon(const sunsky_sequence *seq, sunsky_vec3_in normal, const float *horizon,
                                        int n_sectors, size_t n_profiles, size_t horizon_stride,
                                        const uint8_t *active, size_t n, float *out, size_t out_stride, void *stream);
+
+/* The per-frame irradiance series: what a receiver collects in each frame (an hourly power
+ * profile, a day's illuminance curve, the hour a far wall starts to shade a window), K * P planes
+ * in one call.  Additive: sunsky_sequence_irradiance(_horizon) and their bits are untouched.
+ *
+ * Notation as above: n_l = to_local(n) as given; c_ij and omega the prepared grid's cell centres
+ * and solid angle; sky_{k,p}(c) frame k's term of R_p (reference precision, disc branch off;
+ * spectral: the two-node lerp, an invalid wavelength a plane of zeros); F_k[p] the unweighted flux.
+ *     A^k_p[i, j] = fp32(omega sky_{k,p}(c_ij))          rounded once at prepare time
+ *     E^k_p(n)    = sum_i sum_j A^k_p[i, j] max(0, n_l . c_ij)  +  F_k[p] max(0, n_l . s_k)
+ * and under a horizon profile, by the rule of sunsky_sequence_irradiance_horizon with the same
+ * v_r[i, b], sectors, n_profiles in {1, n}, strides and sun column j_k,
+ *     E^k_p(n_r; h_r) = sum_i sum_j fp32(max(0, n_l . c_ij) v_r[i, b(j)]) A^k_p[i, j]
+ *                     + [s_k.z >= h_r[b_k]] max(0, n_l . s_k) F_k[p].
+ * The weights do not enter: every frame counts, one with w_k = 0 included; the series is each
+ * frame's own irradiance and the caller integrates.  A frame whose sun is below the horizon gives
+ * exact zeros, and so do inactive lanes; a NaN in a profile is unspecified for that receiver only.
+ *
+ * Summation order, per frame and plane: sunsky_sequence_irradiance's for a sequence holding that
+ * one frame -- each row's cells in column order into a row sum from 0 (fma(cos, A, row)), the row
+ * sums in row order, then the frame's one sun (fma(cos_sun, F_k[p], sum)); the dot product is the
+ * forward's, fma(a.z, b.z, fma(a.y, b.y, a.x b.x)); depth n_phi + n_z + 1.  The result does not
+ * depend on n, the lane, the grid, SUNSKY_AMD_BLOCKS_PER_CU, on how frames are grouped in the
+ * staged image or on the sub-range of frames a call asks for.
+ * Consequence: take a one-frame sequence with frame k's direction and turbidity and weight 1,
+ * prepared on the same grid and wavelength list.  Planes [k P, (k + 1) P) of the series are bit
+ * for bit its sunsky_sequence_irradiance output, and under a horizon its
+ * sunsky_sequence_irradiance_horizon output.
+ * Out of scope: gradients of the series, weighted or cumulative-prefix variants, ground
+ * reflection, per-cell visibility, partial shading of a disc.
+ *
+ * sunsky_sequence_prepare_irradiance_series is host-synchronous and needs prepare_irradiance.  It
+ * is sticky exactly as prepare_irradiance_grad is (a later prepare_irradiance restages it,
+ * sunsky_sequence_update drops it with the tables) and independent of it.  One kernel computes
+ * A^k_p for all K frames on the device and writes the staged image there: the frames lie in
+ * groups of G consecutive frames, G = min(8, max(1, 24 / P)) a function of P alone (8 for RGB),
+ * a group's record being a cell direction followed by its G P values, 16-byte aligned; every
+ * frame's s_k, F_k[p] and j_k lie beside them.  K P Q <= 2^26 floats (256 MiB), refused with a
+ * message above that; the environment variable SUNSKY_AMD_IRRADIANCE_SERIES_MAX_FLOATS, read at
+ * prepare time, lowers the cap (a restaging by prepare_irradiance whose tables exceed the cap
+ * leaves the series unprepared).  On a host-only sequence it is a state change, the cap check
+ * included.
+ *
+ * sunsky_sequence_get_irradiance_frame_table returns the P x n_z x n_phi values sky_{k,p}(c_ij) of
+ * frame k, unweighted and not multiplied by omega, with the writing convention of
+ * sunsky_sequence_get_irradiance_table: bit for bit the SKY table of the one-frame, weight-1
+ * sequence.  It needs prepare_irradiance alone and works on host-only sequences (computed on the
+ * host there, on the device otherwise; host-synchronous).
+ *
+ * sunsky_sequence_irradiance_series is a hot-path call: stream-ordered, no allocation, no
+ * host-synchronous call, capturable.  Frame k of [first_frame, first_frame + n_frames) and plane p
+ * go to out + ((k - first_frame) P + p) * out_stride.  horizon == NULL is the open horizon and
+ * ignores n_sectors, n_profiles and horizon_stride.  n == 0 or n_frames == 0 succeeds (nothing
+ * else is looked at); n < 2^32.  Refused with SUNSKY_ERROR_INVALID_VALUE and a message, in this
+ * order: a NULL normal or out; n >= 2^32; a sequence without prepare_irradiance_series;
+ * first_frame < 0, n_frames < 0 or first_frame + n_frames > count; with a horizon, n_sectors < 1
+ * or not a divisor of n_phi, n_profiles other than 1 and n, horizon_stride < n with
+ * n_profiles == n and n_sectors > 1; out_stride < n with more than one output plane; a host-only
+ * sequence, as for the other launches. */
+int sunsky_sequence_prepare_irradiance_series(sunsky_sequence *seq);
+int sunsky_sequence_get_irradiance_frame_table(const sunsky_sequence *seq, int k, float *out, size_t capacity,
+                                               size_t *count);
+int sunsky_sequence_irradiance_series(const sunsky_sequence *seq, sunsky_vec3_in normal, const float *horizon,
+                                      int n_sectors, size_t n_profiles, size_t horizon_stride,
+                                      const uint8_t *active, size_t n, int first_frame, int n_frames,
+                                      float *out, size_t out_stride, void *stream);
 
 /* Gradients of the irradiance with respect to the receiver normals and the frame weights
  * (reverse mode).  Notation as above, with A_p[i, j] = fp32(omega R_p[i, j]) and

@@ -492,6 +492,28 @@ public:
         check(sunsky_sequence_get_irradiance_sun_columns(s_, c.data(), count, &count));
         return c;
     }
+    // The per-frame irradiance series (sunsky_amd.h): every frame's own E^k_p(n), frame k of
+    // [first_frame, first_frame + n_frames) and plane p at out.data + ((k - first_frame) P + p) *
+    // stride.  n_frames < 0: all frames from first_frame on.  horizon == nullptr: the open horizon;
+    // otherwise irradiance_horizon's profile arguments.  Needs prepare_irradiance_series, which is
+    // sticky.  irradiance_frame_table: frame k's own sky table, P x n_z x n_phi.
+    void prepare_irradiance_series() { check(sunsky_sequence_prepare_irradiance_series(s_)); }
+    std::vector<float> irradiance_frame_table(int k) const {
+        size_t count = 0;
+        check(sunsky_sequence_get_irradiance_frame_table(s_, k, nullptr, 0, &count));
+        std::vector<float> t(count);
+        check(sunsky_sequence_get_irradiance_frame_table(s_, k, t.data(), count, &count));
+        return t;
+    }
+    void irradiance_series(Vector3 normal, size_t n, SpectrumOut out, int first_frame = 0, int n_frames = -1,
+                           const uint8_t* active = nullptr, const float* horizon = nullptr, int n_sectors = 0,
+                           bool per_receiver = false, size_t horizon_stride = 0, void* stream = nullptr) const {
+        if (n_frames < 0) n_frames = info().count - first_frame;
+        check(sunsky_sequence_irradiance_series(s_, sunsky_vec3_in{normal.x, normal.y, normal.z}, horizon, n_sectors,
+                                                per_receiver ? n : 1,
+                                                horizon_stride ? horizon_stride : per_receiver ? n : 1, active, n,
+                                                first_frame, n_frames, out.data, out.stride ? out.stride : n, stream));
+    }
     // Gradients of the irradiance with respect to the normals (written, three world-space
     // planes) and the frame weights (accumulated into count floats); either may be left out
     // (a default Vector3Out / nullptr).  Needs prepare_irradiance_grad, which is sticky.

@@ -69,6 +69,12 @@ struct sunsky_sequence {
     DeviceBuffer<float> d_irr_grad;          // every frame's sun | F_k[p] | the reduction workspace
     SeqIrrGrad irr_grad = {};
     size_t irr_grad_cap = 0;                 // the workspace bound in floats, as read at prepare time
+    // the per-frame series (prepare_irradiance_series): sticky as the gradients are; the groups'
+    // images, then the values' sun records, then their sun columns in one block
+    bool irr_series_wanted = false, irr_series_ready = false;
+    DeviceBuffer<float> d_irr_series;
+    SeqIrrSeries irr_series = {};
+    int irr_series_groups = 0;
 
     void require_device() const {
         if (!mod) throw std::invalid_argument("host-only sequence (over a sunsky_emitter_create_host emitter) cannot launch kernels");
@@ -92,6 +98,11 @@ struct sunsky_sequence {
         if (!irr_grad_ready)
             throw std::invalid_argument("the sequence's irradiance gradients are not prepared yet: call "
                                         "sunsky_sequence_prepare_irradiance_grad first");
+    }
+    void require_irradiance_series() const {
+        if (!irr_series_ready)
+            throw std::invalid_argument("the sequence's irradiance series is not prepared yet: call "
+                                        "sunsky_sequence_prepare_irradiance_series first");
     }
     // The snapshot never changes, so an identity to_world takes the identity code object under
     // capture too (SUNSKY_AMD_GENERAL_XFORM=1: the general one always)
@@ -429,8 +440,10 @@ void seq_sampling_finish(sunsky_sequence* q, int nz, int nphi, std::vector<float
 // sunsky_sequence_irradiance_table / _flux on the host (host-only sequences): the same
 // definitions through the SS_HD functions, with the host's libm.  sky: [planes][nz][nphi],
 // flux: [planes][count].
-void seq_irradiance_host(const sunsky_sequence* q, int nz, int nphi, const LambdaSet& L, int planes, float s2,
-                         std::vector<float>& sky_out, std::vector<float>& flux) {
+// The sky table over the frames [k0, k1) with their weights, or (unit) with weight 1: one frame's
+// own table (sunsky_sequence_get_irradiance_frame_table) is the body run for that frame alone.
+void seq_irradiance_sky_host(const sunsky_sequence* q, int nz, int nphi, const LambdaSet& L, int planes, int k0, int k1,
+                             bool unit, float* sky_out) {
     const SunskyKArgs& K = q->kargs;
     const bool rgb = q->variant == kRGB;
     const float cie = (float)kCieYNormalization;
@@ -439,13 +452,14 @@ void seq_irradiance_host(const sunsky_sequence* q, int nz, int nphi, const Lambd
         for (int j = 0; j < nphi; ++j) {
             const float3_ wo = seq_cell_centre(nz, nphi, i, j);
             float acc[kSeqIrrMaxPlanes] = {0};
-            for (int k = 0; k < q->count; ++k) {
+            for (int k = k0; k < k1; ++k) {
                 const SeqFrame<1>* h = seq_header(q, k);
                 const SkyChannel* sky = seq_sky(q, k);
+                const float w = unit ? 1.f : h->weight;
                 const float gamma = unit_angle(mk3(h->sun_n[0], h->sun_n[1], h->sun_n[2]), wo);
                 if (rgb) {
                     for (int c = 0; c < 3; ++c)
-                        acc[c] = fmaf(h->weight, K.sky_scale * render_sky(sky[c], wo.z, gamma) * cie, acc[c]);
+                        acc[c] = fmaf(w, K.sky_scale * render_sky(sky[c], wo.z, gamma) * cie, acc[c]);
                     continue;
                 }
                 for (int p = 0; p < planes; ++p) {
@@ -454,11 +468,19 @@ void seq_irradiance_host(const sunsky_sequence* q, int nz, int nphi, const Lambd
                     if (!(f >= 0.f)) continue;
                     float v = K.sky_scale * render_sky(sky[lo], wo.z, gamma);
                     if (f != 0.f) v = lerpf_(v, K.sky_scale * render_sky(sky[hi], wo.z, gamma), f);
-                    acc[p] = fmaf(h->weight, v, acc[p]);
+                    acc[p] = fmaf(w, v, acc[p]);
                 }
             }
             for (int p = 0; p < planes; ++p) sky_out[(size_t)p * cells + (size_t)i * nphi + j] = acc[p];
         }
+}
+
+void seq_irradiance_host(const sunsky_sequence* q, int nz, int nphi, const LambdaSet& L, int planes, float s2,
+                         std::vector<float>& sky_out, std::vector<float>& flux) {
+    const SunskyKArgs& K = q->kargs;
+    const bool rgb = q->variant == kRGB;
+    const float cie = (float)kCieYNormalization;
+    seq_irradiance_sky_host(q, nz, nphi, L, planes, 0, q->count, false, sky_out.data());
     const float* ds = q->h_sun_rad.data();
     const float ring = kTwoPi / (float)kSeqFluxNphi;
     constexpr int kPoints = kSeqFluxNu * kSeqFluxNphi;
@@ -604,6 +626,95 @@ void seq_stage_irradiance_grad(sunsky_sequence* q) {
     q->irr_grad_ready = true;
 }
 
+// The cap of the series' K * P * n_z * n_phi in floats: kSeqIrrSeriesMaxFloats, or the smaller
+// value SUNSKY_AMD_IRRADIANCE_SERIES_MAX_FLOATS gives (read at every prepare).
+size_t seq_irr_series_cap() {
+    size_t cap = kSeqIrrSeriesMaxFloats;
+    if (const char* e = std::getenv("SUNSKY_AMD_IRRADIANCE_SERIES_MAX_FLOATS")) {
+        const long long v = std::atoll(e);
+        if (v >= 1 && (unsigned long long)v < cap) cap = (size_t)v;
+    }
+    return cap;
+}
+
+// sunsky_sequence_irradiance_series_table over `groups` groups of `group` frames from frame0:
+// into the groups' images, or (raw) one frame's plain table.  The caller synchronises.
+void seq_irr_series_table(const sunsky_sequence* q, float* image, float* raw, int group, int groups, int frame0) {
+    SeqIrrSeriesTableArgs T;
+    std::memset(&T, 0, sizeof(T));
+    T.image = image;
+    T.raw = raw;
+    T.cells = q->irr.cells;
+    T.cells_rec = seq_irr_record(q->irr_planes);
+    T.L = q->irr_L;
+    T.nz = q->irr_nz;
+    T.nphi = q->irr_nphi;
+    T.planes = q->irr_planes;
+    T.group = group;
+    T.groups = groups;
+    T.rec = seq_irr_record(group * q->irr_planes);
+    T.frame0 = frame0;
+    T.omega = q->irr_omega;
+    const SunskyKArgs* K = q->d_state.get();
+    SeqArgs A = q->args();
+    void* args[] = {&K, &A, &T};
+    const size_t lanes = (size_t)q->irr_nz * (size_t)q->irr_nphi * (size_t)groups;
+    launch(q->mod, K_SEQUENCE_IRRADIANCE_SERIES_TABLE,
+           grid_for(q->mod, K_SEQUENCE_IRRADIANCE_SERIES_TABLE, lanes, /*tunable=*/false), kBlock, nullptr, args);
+}
+
+// What sunsky_sequence_irradiance_series walks, for the tables as they are now: every group's
+// image written on the device, then per value its frame's sun record and column.  Refuses above
+// the cap (`quiet`: leaves the series unprepared instead); a host-only sequence only changes state.
+void seq_stage_irradiance_series(sunsky_sequence* q, bool quiet = false) {
+    q->irr_series_ready = false;
+    const int planes = q->irr_planes, count = q->count;
+    const size_t cells = (size_t)q->irr_nz * (size_t)q->irr_nphi, cap = seq_irr_series_cap();
+    if ((size_t)count * (size_t)planes * cells > cap) {
+        if (quiet) return;
+        throw std::invalid_argument("the irradiance series of " + std::to_string(count) + " frames x " + std::to_string(planes) +
+                                    " planes x " + std::to_string(cells) + " cells exceeds the cap of " + std::to_string(cap) +
+                                    " floats (2^26, lowered by SUNSKY_AMD_IRRADIANCE_SERIES_MAX_FLOATS)");
+    }
+    if (q->device >= 0) {
+        q->d_irr_series.reset();
+        const int G = seq_irr_series_group(planes), values = G * planes, rec = seq_irr_record(values);
+        const int groups = (count + G - 1) / G;
+        const size_t image = cells * (size_t)rec, images = image * (size_t)groups, nvalues = (size_t)groups * values;
+        static_assert(sizeof(int) == sizeof(float), "the values' columns lie behind their sun records");
+        q->d_irr_series.alloc(images + 5 * nvalues);
+        float* const d = q->d_irr_series.get();
+        hip_check(hipMemset(d, 0, sizeof(float) * images), "hipMemset");
+        seq_irr_series_table(q, d, nullptr, G, groups, 0);
+        std::vector<float> suns(5 * nvalues, 0.f);   // {s_k.xyz, F_k[p]} per value, then the columns
+        int* const cols = reinterpret_cast<int*>(suns.data() + 4 * nvalues);
+        for (int k = 0; k < count; ++k) {
+            const SeqFrame<1>* h = seq_header(q, k);
+            for (int p = 0; p < planes; ++p) {
+                const size_t v = (size_t)k * planes + p;   // group k / G, value (k % G) * planes + p
+                float* r = &suns[4 * v];
+                r[0] = h->sun_n[0]; r[1] = h->sun_n[1]; r[2] = h->sun_n[2];
+                r[3] = q->irr_flux[(size_t)p * count + k];
+                cols[v] = q->irr_sun_cols[(size_t)k];
+            }
+        }
+        hip_check(hipMemcpy(d + images, suns.data(), sizeof(float) * suns.size(), hipMemcpyHostToDevice), "hipMemcpy");
+        hip_check(hipStreamSynchronize(nullptr), "hipStreamSynchronize");
+        SeqIrrSeries& s = q->irr_series;
+        std::memset(&s, 0, sizeof(s));
+        s.images = d;
+        s.suns = d + images;
+        s.sun_cols = reinterpret_cast<const int*>(d + images + 4 * nvalues);
+        s.image_floats = image;
+        s.nz = q->irr_nz;
+        s.nphi = q->irr_nphi;
+        s.values = values;
+        s.rec = rec;
+        q->irr_series_groups = groups;
+    }
+    q->irr_series_ready = true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -693,6 +804,7 @@ int sunsky_sequence_update(sunsky_sequence* seq, const float* sun_dirs, const fl
         seq->samp_nz = seq->samp_nphi = 0;
         seq->irr_nz = seq->irr_nphi = seq->irr_planes = 0;   // and so did the irradiance tables
         seq->irr_grad_ready = false;                         // and what their gradients read (wanted stays)
+        seq->irr_series_ready = false;                       // and the per-frame series (wanted stays)
         if (seq->grad_ready) seq_stage_grad(seq);
     });
 }
@@ -1042,8 +1154,11 @@ int sunsky_sequence_prepare_irradiance(sunsky_sequence* seq, int n_z, int n_phi,
             seq->irr_planes = planes;
             seq->irr_L = T.L;
             if (seq->irr_grad_wanted) seq_stage_irradiance_grad(seq);   // sticky: restaged for the new tables
+            // ... and so is the series (tables above its cap leave it unprepared)
+            if (seq->irr_series_wanted) seq_stage_irradiance_series(seq, /*quiet=*/true);
         };
         seq->irr_grad_ready = false;
+        seq->irr_series_ready = false;
         if (seq->device < 0) {
             seq_irradiance_host(seq, n_z, n_phi, T.L, planes, T.sin2_half_ap, sky, flux);
             accept();
@@ -1159,6 +1274,85 @@ int sunsky_sequence_irradiance_horizon(const sunsky_sequence* seq, sunsky_vec3_i
                            n_profiles == 1 ? 0 : 1, 0};
         void* args[] = {&lc.K, &S, &Z, (void*)&nrm.x, (void*)&nrm.y, (void*)&nrm.z, &active, &n, &out, &ostride};
         lc.run(seq->variant == kSpectral ? K_SEQUENCE_IRRADIANCE_HORIZON_SPEC : K_SEQUENCE_IRRADIANCE_HORIZON_RGB, n, args);
+    });
+}
+
+int sunsky_sequence_prepare_irradiance_series(sunsky_sequence* seq) {
+    SUNSKY_PHASE("InitScene", "sequence_prepare_irradiance_series");
+    if (!seq) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sequence");
+    return guarded([&] {
+        seq->require_irradiance();
+        DeviceScope g(seq->device);   // host-only (-1): no device to scope
+        // nothing may still read the old images
+        if (seq->device >= 0) hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        seq_stage_irradiance_series(seq);
+        seq->irr_series_wanted = true;
+    });
+}
+
+int sunsky_sequence_get_irradiance_frame_table(const sunsky_sequence* seq, int k, float* out, size_t cap, size_t* count) {
+    if (!seq) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sequence");
+    return guarded([&] {
+        seq->require_irradiance();
+        if (k < 0 || k >= seq->count) throw std::invalid_argument("frame index out of range");
+        const size_t total = (size_t)seq->irr_planes * (size_t)seq->irr_nz * (size_t)seq->irr_nphi;
+        if (count) *count = total;
+        if (!out || !cap) return;
+        std::vector<float> t(total, 0.f);
+        if (seq->device < 0) {
+            seq_irradiance_sky_host(seq, seq->irr_nz, seq->irr_nphi, seq->irr_L, seq->irr_planes, k, k + 1, /*unit=*/true,
+                                    t.data());
+        } else {
+            DeviceScope g(seq->device);
+            DeviceBuffer<float> d;
+            d.alloc(total);
+            hip_check(hipMemset(d.get(), 0, sizeof(float) * total), "hipMemset");
+            seq_irr_series_table(seq, nullptr, d.get(), 1, 1, k);
+            hip_check(hipStreamSynchronize(nullptr), "hipStreamSynchronize");
+            hip_check(hipMemcpy(t.data(), d.get(), sizeof(float) * total, hipMemcpyDeviceToHost), "hipMemcpy");
+        }
+        std::memcpy(out, t.data(), sizeof(float) * std::min(cap, total));
+    });
+}
+
+int sunsky_sequence_irradiance_series(const sunsky_sequence* seq, sunsky_vec3_in nrm, const float* horizon, int n_sectors,
+                                      size_t n_profiles, size_t hstride, const uint8_t* active, size_t n, int first_frame,
+                                      int n_frames, float* out, size_t ostride, void* stream) {
+    SUNSKY_PHASE("EndpointEvaluate", "sequence_irradiance_series");
+    if (!seq) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sequence");
+    if (n == 0 || n_frames == 0) return SUNSKY_OK;
+    if (!nrm.x || !nrm.y || !nrm.z || !out) return fail(SUNSKY_ERROR_INVALID_VALUE, "null normal / output pointer");
+    if (n > 0xffffffffull) return fail(SUNSKY_ERROR_INVALID_VALUE, "more than 2^32 receivers");
+    return guarded([&] {
+        seq->require_irradiance_series();   // first: the message names the missing call on any sequence
+        if (first_frame < 0 || n_frames < 0 || (long long)first_frame + n_frames > seq->count)
+            throw std::invalid_argument("frame range out of range: 0 <= first_frame, 0 <= n_frames, first_frame + n_frames <= count");
+        if (horizon) {
+            if (n_sectors < 1 || seq->irr_nphi % n_sectors != 0)
+                throw std::invalid_argument("n_sectors must be >= 1 and divide the irradiance tables' n_phi");
+            if (n_profiles != 1 && n_profiles != n) throw std::invalid_argument("n_profiles must be 1 or n");
+            if (n_profiles == n && n_sectors > 1 && hstride < n) throw std::invalid_argument("horizon_stride < n");
+        }
+        const int planes = seq->irr_planes, G = seq_irr_series_group(planes);
+        if ((long long)n_frames * planes > 1 && ostride < n) throw std::invalid_argument("out_stride < n");
+        Launcher lc(seq, stream);
+        SeqIrrSeries S = seq->irr_series;
+        S.plane0 = (long long)first_frame * planes;
+        S.n_planes = (long long)n_frames * planes;
+        S.group0 = first_frame / G;
+        S.n_groups = (first_frame + n_frames - 1) / G - S.group0 + 1;
+        // one workgroup per work item (tile of receiver pairs, group), grid-stride over the items
+        const size_t pairs = (n + 1) / 2, tiles = (pairs + kBlock - 1) / kBlock, items = tiles * (size_t)S.n_groups;
+        const bool spec = seq->variant == kSpectral;
+        if (!horizon) {
+            void* args[] = {&lc.K, &S, (void*)&nrm.x, (void*)&nrm.y, (void*)&nrm.z, &active, &n, &out, &ostride};
+            lc.run(spec ? K_SEQUENCE_IRRADIANCE_SERIES_SPEC : K_SEQUENCE_IRRADIANCE_SERIES_RGB, items * kBlock, args);
+        } else {
+            SeqIrrHorizon Z = {horizon, nullptr, hstride, n_sectors, seq->irr_nphi / n_sectors, n_profiles == 1 ? 0 : 1, 0};
+            void* args[] = {&lc.K, &S, &Z, (void*)&nrm.x, (void*)&nrm.y, (void*)&nrm.z, &active, &n, &out, &ostride};
+            lc.run(spec ? K_SEQUENCE_IRRADIANCE_SERIES_HORIZON_SPEC : K_SEQUENCE_IRRADIANCE_SERIES_HORIZON_RGB, items * kBlock,
+                   args);
+        }
     });
 }
 

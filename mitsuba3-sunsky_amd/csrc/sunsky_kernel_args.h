@@ -282,6 +282,57 @@ struct SeqIrrHorizon {
 };
 static_assert(sizeof(SeqIrrHorizon) == 40 && offsetof(SeqIrrHorizon, sectors) == 24, "SeqIrrHorizon layout");
 
+// ---------------------------------------------------------------- per-frame irradiance series
+// sunsky_sequence_prepare_irradiance_series / sunsky_sequence_irradiance_series (sunsky_amd.h has
+// the definition).  The frames are staged in groups of G consecutive frames, G a function of the
+// plane count P alone: as many frames as fit kSeqIrrSeriesWidth values, at most
+// kSeqIrrSeriesMaxGroup, at least one (RGB: 8 frames, 24 values).  A group's image is the
+// forward's image with G * P "planes": per cell one record c_ij.xyz, then value g * P + p =
+// A^{kG+g}_p[i, j], padded to 16 bytes (seq_irr_record(G * P)); a frame past the last one holds
+// zeros.  Beside the images lie one 16-byte sun record {s_k.xyz, F_k[p]} and one sun column j_k
+// per value.  A work item of the hot path is (receiver pair, group); value v of group gr is
+// output plane gr * G * P + v - first_frame * P, stored when it falls into the call's range.
+constexpr int kSeqIrrSeriesWidth = 24;       // values per group: the widest pass of the contraction
+constexpr int kSeqIrrSeriesMaxGroup = 8;     // frames per group at most
+constexpr size_t kSeqIrrSeriesMaxFloats = (size_t)1 << 26;   // the cap of K * P * n_z * n_phi
+constexpr int seq_irr_series_group(int planes) {
+    return kSeqIrrSeriesWidth / planes < 1 ? 1
+           : kSeqIrrSeriesWidth / planes > kSeqIrrSeriesMaxGroup ? kSeqIrrSeriesMaxGroup : kSeqIrrSeriesWidth / planes;
+}
+static_assert(seq_irr_series_group(3) == 8 && seq_irr_series_group(1) == 8 && seq_irr_series_group(5) == 4 &&
+              seq_irr_series_group(kSeqIrrMaxPlanes) == 1, "group size");
+
+// sunsky_sequence_irradiance_series_table: one lane per (cell, group).  Writes the groups' images
+// (image != nullptr: `groups` groups of `group` frames from frame `frame0`, records of `rec`
+// floats, value = omega * sky, direction = the forward image's, which the host computed) or one frame's plain table (raw != nullptr: [planes][nz][nphi] of
+// frame `frame0`, group = groups = 1, value = sky).
+struct SeqIrrSeriesTableArgs {
+    float* image;
+    float* raw;
+    const float* cells;        // the forward's image: a record's direction is copied from its cell record
+    LambdaSet L;
+    int nz, nphi, planes;
+    int group, groups, rec, frame0;
+    float omega;
+    int cells_rec;             // floats of one record of the forward's image
+};
+static_assert(offsetof(SeqIrrSeriesTableArgs, nz) == 24 + sizeof(LambdaSet) &&
+              sizeof(SeqIrrSeriesTableArgs) == 24 + sizeof(LambdaSet) + 36, "SeqIrrSeriesTableArgs layout");
+
+// The hot path's view of the staged series and of one call's range of frames
+struct SeqIrrSeries {
+    const float* images;       // [groups] images of nz * nphi records of `rec` floats
+    const float* suns;         // [groups][values] records {s_k.xyz, F_k[p]}
+    const int* sun_cols;       // [groups][values] column j_k of the value's frame
+    size_t image_floats;       // floats of one group's image: nz * nphi * rec
+    long long plane0;          // first_frame * planes: value v of group gr is plane gr * values + v - plane0
+    long long n_planes;        // n_frames * planes: the planes the call stores
+    int nz, nphi;
+    int values, rec;           // G * P, and seq_irr_record(values)
+    int group0, n_groups;      // the groups the call's frames lie in
+};
+static_assert(sizeof(SeqIrrSeries) == 72 && offsetof(SeqIrrSeries, nz) == 48, "SeqIrrSeries layout");
+
 // ---------------------------------------------------------------- gradients of the sequence irradiance
 // sunsky_sequence_prepare_irradiance_grad / sunsky_sequence_irradiance_vjp (sunsky_amd.h has the
 // definition).  The weight gradient goes through the adjoint image: per slice of receivers one

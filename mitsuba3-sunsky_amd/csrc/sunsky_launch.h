@@ -103,6 +103,10 @@ std::string default_pack_path();   // SUNSKY_AMD_DATASET, else the pack beside t
     X(SEQUENCE_IRRADIANCE_SPEC, "sunsky_sequence_irradiance_spec", 64, false, 2, FOUR)             \
     X(SEQUENCE_IRRADIANCE_HORIZON_RGB, "sunsky_sequence_irradiance_horizon_rgb", 64, false, 2, FOUR) \
     X(SEQUENCE_IRRADIANCE_HORIZON_SPEC, "sunsky_sequence_irradiance_horizon_spec", 64, false, 2, FOUR) \
+    X(SEQUENCE_IRRADIANCE_SERIES_RGB, "sunsky_sequence_irradiance_series_rgb", 64, false, 1, FOUR) \
+    X(SEQUENCE_IRRADIANCE_SERIES_SPEC, "sunsky_sequence_irradiance_series_spec", 64, false, 1, FOUR) \
+    X(SEQUENCE_IRRADIANCE_SERIES_HORIZON_RGB, "sunsky_sequence_irradiance_series_horizon_rgb", 64, false, 1, FOUR) \
+    X(SEQUENCE_IRRADIANCE_SERIES_HORIZON_SPEC, "sunsky_sequence_irradiance_series_horizon_spec", 64, false, 1, FOUR) \
     X(SEQUENCE_IRRADIANCE_VJP_NORMAL_RGB, "sunsky_sequence_irradiance_vjp_normal_rgb", 64, false, 2, FOUR) \
     X(SEQUENCE_IRRADIANCE_VJP_NORMAL_SPEC, "sunsky_sequence_irradiance_vjp_normal_spec", 64, false, 2, FOUR) \
     X(SEQUENCE_IRRADIANCE_ADJOINT, "sunsky_sequence_irradiance_adjoint", kSeqIrrGradAdjointBlocksPerCu, false, 1, FOUR) \
@@ -128,7 +132,8 @@ std::string default_pack_path();   // SUNSKY_AMD_DATASET, else the pack beside t
     X(SEQUENCE_SUNS, "sunsky_sequence_suns", 0, false, 1, PLAIN)                                   \
     X(SEQUENCE_GRAD_REDUCE, "sunsky_sequence_grad_reduce", 0, false, 1, PLAIN)                     \
     X(SEQUENCE_IRRADIANCE_TABLE, "sunsky_sequence_irradiance_table", 64, false, 1, PLAIN)          \
-    X(SEQUENCE_IRRADIANCE_FLUX, "sunsky_sequence_irradiance_flux", 0, false, 1, PLAIN)
+    X(SEQUENCE_IRRADIANCE_FLUX, "sunsky_sequence_irradiance_flux", 0, false, 1, PLAIN)               \
+    X(SEQUENCE_IRRADIANCE_SERIES_TABLE, "sunsky_sequence_irradiance_series_table", 64, false, 1, PLAIN)
 
 #define X(id, name, wg, dir, per, forms) K_##id,
 enum KernelId { SUNSKY_KERNELS(X) K_COUNT };

@@ -76,6 +76,16 @@ SEQ_GRAD_BLOCKS_PER_CU, SEQ_GRAD_WORKSPACE_FLOATS, SEQ_GRAD_LDS_FRAMES = 16, 1 <
 # environment variable that lowers it
 SEQ_IRR_GRAD_CHUNK, SEQ_IRR_GRAD_SLICE_MIN, SEQ_IRR_GRAD_MAX_SLICES, SEQ_IRR_GRAD_WORKSPACE_FLOATS = 256, 1024, 64, 1 << 22
 SEQ_IRR_GRAD_WORKSPACE_ENV = "SUNSKY_AMD_IRRADIANCE_GRAD_WORKSPACE_FLOATS"
+# sunsky_sequence_irradiance_series' staging (csrc/sunsky_kernel_args.h, include/sunsky_amd.h): the
+# values of a frame group, the most frames in one, the cap of K P Q in floats and the environment
+# variable that lowers it
+SEQ_IRR_SERIES_WIDTH, SEQ_IRR_SERIES_MAX_GROUP, SEQ_IRR_SERIES_MAX_FLOATS = 24, 8, 1 << 26
+SEQ_IRR_SERIES_MAX_ENV = "SUNSKY_AMD_IRRADIANCE_SERIES_MAX_FLOATS"
+
+
+def seq_irr_series_group(planes):
+    """G, the frames of one staged group of the irradiance series: a function of the plane count alone."""
+    return max(1, min(SEQ_IRR_SERIES_MAX_GROUP, SEQ_IRR_SERIES_WIDTH // planes))
 
 
 def seq_irr_grad_shape(n, planes, cells, count, cap=SEQ_IRR_GRAD_WORKSPACE_FLOATS):
@@ -153,6 +163,10 @@ _SIGS = {
     "sunsky_sequence_get_irradiance_sun_columns": (C.c_int, [vp, C.POINTER(C.c_int), C.c_size_t, C.POINTER(C.c_size_t)]),
     "sunsky_sequence_irradiance_horizon": (C.c_int, [vp, Vec3In, vp, C.c_int, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp,
                                                      C.c_size_t, vp]),
+    "sunsky_sequence_prepare_irradiance_series": (C.c_int, [vp]),
+    "sunsky_sequence_get_irradiance_frame_table": (C.c_int, [vp, C.c_int, c_float_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "sunsky_sequence_irradiance_series": (C.c_int, [vp, Vec3In, vp, C.c_int, C.c_size_t, C.c_size_t, vp, C.c_size_t,
+                                                    C.c_int, C.c_int, vp, C.c_size_t, vp]),
     "sunsky_sequence_prepare_irradiance_grad": (C.c_int, [vp]),
     "sunsky_sequence_irradiance_vjp": (C.c_int, [vp, Vec3In, vp, C.c_size_t, vp, C.c_size_t, Vec3Out, vp, vp]),
     "sunsky_direct_diffuse": (C.c_int, [vp, Vec3In, vp, vp, C.c_int, C.c_size_t, C.c_uint32, C.c_uint32,

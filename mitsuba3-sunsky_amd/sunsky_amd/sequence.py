@@ -370,6 +370,87 @@ class SunskySequence:
                                                            _ptr(mask), n, _ptr(out), out.stride(0), self._stream()))
         return out
 
+    # ------------------------------------------------------------ per-frame irradiance series
+    def prepare_irradiance_series(self):
+        """Stages every frame's own sky image for irradiance_series
+        (sunsky_sequence_prepare_irradiance_series): K x P x n_z x n_phi values computed and kept on
+        the device, at most 2^26.  Needs prepare_irradiance; sticky: a later prepare_irradiance
+        restages it, update() drops it with the tables.  Host-synchronous; a state change only on
+        host-only sequences."""
+        check(lib().sunsky_sequence_prepare_irradiance_series(self._h))
+
+    def irradiance_frame_table(self, k):
+        """Frame k's own sky table as fp32 (P, n_z, n_phi): sky_{k,p} at the cell centres, not
+        weighted and not multiplied by omega -- the "sky" table of a sequence that holds frame k
+        alone with weight 1.  Needs prepare_irradiance; works on host-only sequences."""
+        cnt = C.c_size_t()
+        check(lib().sunsky_sequence_get_irradiance_frame_table(self._h, int(k), None, 0, C.byref(cnt)))
+        buf = (C.c_float * cnt.value)()
+        check(lib().sunsky_sequence_get_irradiance_frame_table(self._h, int(k), buf, cnt.value, C.byref(cnt)))
+        i = self.irradiance_info()
+        return np.array(buf, dtype=np.float32).reshape(i["n_planes"], i["n_z"], i["n_phi"])
+
+    def _frames(self, frames):
+        """A frames argument as (first, count): None (all), a (first, count) pair or a range of step 1."""
+        k = len(self)
+        if frames is None:
+            return 0, k
+        if isinstance(frames, range):
+            if frames.step != 1:
+                raise ValueError("frames must be None, a (first, count) pair or a range with step 1")
+            first, count = (frames.start, len(frames)) if len(frames) else (0, 0)
+        else:
+            try:
+                first, count = frames
+                ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (first, count))
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError("frames must be None, a (first, count) pair or a range with step 1")
+            first, count = int(first), int(count)
+        if first < 0 or count < 0 or first + count > k:
+            raise ValueError(f"frames ({first}, {count}) are not within the sequence's {k} frames")
+        return first, count
+
+    def irradiance_series(self, normals, frames=None, active=None, out=None, horizon=None):
+        """Every frame's own irradiance on receivers with world-space normals (3, n) ->
+        (n_frames, P, n): E^k_p(n) of sunsky_sequence_irradiance_series, bit for bit what
+        irradiance() gives for a sequence that holds frame k alone with weight 1.  The weights do
+        not enter (the caller integrates); night frames give exact zeros.
+
+        frames: None (all), a (first, count) pair or a range with step 1.  `out` may have a row
+        stride, as irradiance's; `horizon` takes irradiance's forms.  Needs prepare_irradiance_series."""
+        first, count = self._frames(frames)
+        if self.device is None:
+            # the library refuses, and says first which preparation is missing; it reads no pointer
+            p = C.cast((C.c_float * 1)(), C.c_void_p)
+            check(lib().sunsky_sequence_irradiance_series(self._h, Vec3In(p, p, p), None, 0, 0, 0, None, 1, 0, 1, p, 1, None))
+            raise ValueError("host-only sequence (over a host-only emitter) cannot launch kernels")
+        nrm, vin = SunskyEmitter._vec_in(self, normals)
+        n = nrm.shape[1]
+        planes = self.irradiance_info()["n_planes"]
+        sectors = profiles = hstride = 0
+        if horizon is not None:
+            horizon, sectors, profiles, hstride = self._horizon(horizon, n)
+        shape = (count, planes, n)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != self.device
+              or tuple(out.shape) != shape):
+            raise ValueError(f"out must be a float32 tensor of shape {shape} on {self.device}")
+        row = n
+        if count * planes > 1 and n > 0:
+            row = out.stride(1) if planes > 1 else out.stride(0)
+            if not (out.is_contiguous() or ((n == 1 or out.stride(2) == 1) and row >= n
+                                            and (count == 1 or planes == 1 or out.stride(0) == planes * row))):
+                raise ValueError("out planes must be contiguous (a row stride is allowed)")
+        elif not out.is_contiguous() and n > 1 and out.stride(2) != 1:
+            raise ValueError("out planes must be contiguous (a row stride is allowed)")
+        mask = SunskyEmitter._mask(self, active, n)
+        check(lib().sunsky_sequence_irradiance_series(self._h, vin, _ptr(horizon), sectors, profiles, hstride, _ptr(mask), n,
+                                                      first, count, _ptr(out), row, self._stream()))
+        return out
+
     # ------------------------------------------------------------ gradients and updates
     def update(self, sun_directions=None, turbidity=None, weights=None):
         """Replaces the frames in place (sunsky_sequence_update): the same count, None keeps the

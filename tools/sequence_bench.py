@@ -19,7 +19,9 @@ does an eval's transcendental work with no HBM traffic).  Not part of bench.py.
                 formulations of both gradients (see irradiance_grad()).
   --irradiance-horizon -- instead: sequence.irradiance under a shared and a per-receiver horizon
                 profile beside the unoccluded call and the masked chunked torch formulation
-                (see irradiance_horizon())."""
+                (see irradiance_horizon()).
+  --irradiance-series -- instead: sequence.irradiance_series, every frame's own irradiance in one
+                call, beside K one-frame sequences' irradiance calls (see irradiance_series())."""
 import json
 import os
 import statistics
@@ -389,14 +391,107 @@ def irradiance_grad(ks, dev):
     print("sequence_bench irradiance-grad done")
 
 
+def irradiance_series(ks, dev):
+    """--irradiance-series: every frame's own irradiance on 2^20 receivers (RGB, normals uniform on
+    the sphere, 64 x 256 cells) in one call per frame sub-range, open and under per-receiver
+    horizons of 32 sectors, against two yardsticks of the same session: (a) irradiance() of the
+    weighted sequence once, and (b) what a user writes without the series, K one-frame sequences
+    prepared beforehand (their preparation not counted), each irradiance() into its slice.
+
+    The output of K frames is K x 3 x n floats (4.6 GB at K = 365), so both sides write sub-ranges
+    of at most 64 frames (a multiple of the group size, so no group is walked twice) into one
+    reused 64 x 3 x n buffer; a time is the sum over the sub-ranges.  The largest difference to
+    (b), which must be 0, is taken sub-range by sub-range in an untimed pass.
+
+    The derived issue floor: per record, receiver pair and group of 8 frames 5 + 24 wave
+    instructions of 4 cycles on 1024 SIMDs, at the GFX clock polled while the series runs."""
+    n, nz, nphi, sectors, span = 1 << 20, 64, 256, 32, 64
+    g = torch.Generator(device=dev).manual_seed(5)
+    v = torch.randn((3, n), device=dev, generator=g)
+    nrm = (v / v.norm(dim=0, keepdim=True)).contiguous()
+    hz = (torch.rand((sectors, n), device=dev, generator=g) * 1.4 - 0.2).contiguous()
+    base = {"type": "sunsky", "sun_direction": [0.3, 0.4, 0.866], "turbidity": 3.0, "albedo": 0.2}
+    for k in ks:
+        dirs, turb, wts = frames(k)
+        parent = ss.load_dict(dict(base))
+        seq = ss.SunskySequence(parent, dirs, turb, wts)
+        seq.prepare_irradiance(nz, nphi)
+        t0 = time.perf_counter()
+        seq.prepare_irradiance_series()
+        t_prep = (time.perf_counter() - t0) * 1e3
+        ones = []
+        for i in range(k):
+            one = ss.SunskySequence(parent, dirs[i:i + 1], turb[i:i + 1], [1.0])
+            one.prepare_irradiance(nz, nphi)
+            ones.append(one)
+        group = ss._capi.seq_irr_series_group(3)
+        assert span % group == 0
+        ranges = [(f, min(span, k - f)) for f in range(0, k, span)]
+        buf, buf_b = torch.empty((min(span, k), 3, n), device=dev), torch.empty((min(span, k), 3, n), device=dev)
+        out = torch.empty((3, n), device=dev)
+
+        def series(horizon=None):
+            for f, c in ranges:
+                seq.irradiance_series(nrm, frames=(f, c), out=buf[:c], horizon=horizon)
+
+        def loop(horizon=None, f0=0, count=k):
+            for i in range(f0, f0 + count):
+                ones[i].irradiance(nrm, out=buf_b[(i - f0) % span], horizon=horizon)
+
+        def clock_during(step):
+            """Median GFX clock in MHz polled on the host while step's launches run (None: no reading)."""
+            done = torch.cuda.Event()
+            samples = []
+            try:
+                step()
+                done.record()
+                while not done.query():
+                    samples.append(torch.cuda.clock_rate())
+            except Exception:
+                samples = []
+            torch.cuda.synchronize()
+            return statistics.median(samples) if samples else None
+
+        line = {"K": k, "n": n, "table": [nz, nphi], "group": group, "sub_ranges": len(ranges),
+                "prepare_irradiance_series_ms": round(t_prep, 3)}
+        t_once, all_once = median_ms(lambda: seq.irradiance(nrm, out=out))
+        line["irradiance_once_ms"] = round(t_once, 3)
+        for name, horizon in (("open", None), ("horizon", hz)):
+            t_s, all_s = median_ms(lambda: series(horizon))
+            t_b, all_b = median_ms(lambda: loop(horizon))
+            mhz = clock_during(lambda: series(horizon))
+            worst = 0.0
+            for f, c in ranges:   # untimed: the two sides of every sub-range, bit for bit
+                seq.irradiance_series(nrm, frames=(f, c), out=buf[:c], horizon=horizon)
+                loop(horizon, f, c)
+                worst = max(worst, float((buf[:c] - buf_b[:c]).abs().max().item()))
+            work = n * nz * nphi * k
+            line[name] = {"series_ms": round(t_s, 3), "one_frame_loop_ms": round(t_b, 3), "loop_over_series": round(t_b / t_s, 3),
+                          "receiver_cell_frames_per_s": round(work / (t_s * 1e-3), 0),
+                          "max_abs_diff_to_loop": worst,
+                          "series_ms_all": [round(t, 3) for t in all_s], "one_frame_loop_ms_all": [round(t, 3) for t in all_b]}
+            if mhz:
+                groups = -(-k // group)
+                floor_ms = (n / 128) * nz * nphi * groups * 29 * 4 / (1024 * mhz * 1e6) * 1e3
+                line[name].update({"gfx_clock_mhz": mhz, "issue_floor_ms": round(floor_ms, 3),
+                                   "share_of_issue_floor": round(floor_ms / t_s, 3)})
+        line["irradiance_once_ms_all"] = [round(t, 3) for t in all_once]
+        print(json.dumps(line), flush=True)
+        del ones, buf, buf_b
+    print("sequence_bench irradiance-series done")
+
+
 def main():
-    flags = ("--sampling", "--grad", "--no-loop", "--irradiance", "--irradiance-grad", "--irradiance-horizon")
+    flags = ("--sampling", "--grad", "--no-loop", "--irradiance", "--irradiance-grad", "--irradiance-horizon",
+             "--irradiance-series")
     args = [a for a in sys.argv[1:] if a not in flags]
     ks = [int(a) for a in args] or [24, 365]
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     if "--sampling" in sys.argv[1:]:
         return sampling(ks, dev)
+    if "--irradiance-series" in sys.argv[1:]:
+        return irradiance_series(ks, dev)
     if "--irradiance" in sys.argv[1:]:
         return irradiance(ks, dev)
     if "--irradiance-grad" in sys.argv[1:]:
