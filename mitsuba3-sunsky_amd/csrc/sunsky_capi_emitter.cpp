@@ -525,8 +525,10 @@ static int eval_impl(const sunsky_emitter* e, sunsky_vec3_in w, const float* lam
                 lc.run(vec ? K_EVAL_RGB_V4 : K_EVAL_RGB_V1, cnt, args, dir);
             });
         } else {
-            // the wavelength planes too; their stride matters only when there is a second plane
-            const size_t n4 = vec4_count(n, {w.x, w.y, w.z, out, lam}, {ostride, nlam == 1 ? 0 : lstride}, active);
+            // the wavelength planes too; either stride matters only when there is a second plane
+            // (check_ray_strides): an odd stride next to a single plane keeps the vector kernels
+            const size_t n4 = vec4_count(n, {w.x, w.y, w.z, out, lam}, {nlam == 1 ? 0 : ostride, nlam == 1 ? 0 : lstride},
+                                         active);
             int nl = nlam;
             vec4_then_tail(n, n4, [&](size_t off, size_t cnt, bool vec) {
                 const float *x = w.x + off, *y = w.y + off, *z = w.z + off, *l = lam + off;
@@ -570,7 +572,8 @@ int sunsky_eval_spectral_broadcast(const sunsky_emitter* e, sunsky_vec3_in w, co
     return guarded([&] {
         Launcher lc(e, stream);
         float sign = -1.f;
-        const size_t n4 = vec4_count(n, {w.x, w.y, w.z, out}, {ostride}, active);
+        // one wavelength: out_stride is unused (no second plane), whatever its value
+        const size_t n4 = vec4_count(n, {w.x, w.y, w.z, out}, {m == 1 ? 0 : ostride}, active);
         vec4_then_tail(n, n4, [&](size_t off, size_t cnt, bool vec) {
             const float *x = w.x + off, *y = w.y + off, *z = w.z + off;
             const uint8_t* a = active ? active + off : nullptr;
