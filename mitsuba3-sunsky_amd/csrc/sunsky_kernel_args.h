@@ -1,6 +1,6 @@
 // sunsky_kernel_args.h -- the structs that kernels take by value (beside SunskyKArgs,
 // sunsky_types.h, and TangentArgs, sunsky_staging.h): one definition, read by the kernels
-// (sunsky_kernels.hip), by the C-ABI layer that fills them (sunsky_capi_*.cpp) and by
+// (sunsky_kernels.hip and its parts, kernels/*.h), by the C-ABI layer that fills them (sunsky_capi_*.cpp) and by
 // tools/kbench.cpp.  The sizes are pinned so that the host compiler and the device
 // compiler each check the layout they pass / read.
 #pragma once

@@ -42,27 +42,16 @@
 using namespace sunsky;
 
 #define SS_BLOCK 256
-#ifndef SS_NODES_ATTR       // tuning builds only (tools/gpu_ab2.sh): occupancy attributes
-#define SS_NODES_ATTR
-#endif
-#ifndef SS_RAYS_ATTR         // tuning builds only: occupancy attribute of the per-ray spectral eval
-#define SS_RAYS_ATTR
-#endif
-#ifndef SS_RGB_ATTR
-#define SS_RGB_ATTR
-#endif
-#ifndef SS_SPEC_SAMPLE_ATTR
-#define SS_SPEC_SAMPLE_ATTR
-#endif
-#ifndef SS_RGB_SORTED_ATTR   // probe builds (tools/build) set occupancy attributes here
+// Occupancy attributes of the entry points, by family (empty: the compiler's choice), and the
+// window of the wave-sorted RGB samplers.  tools/mk_probe.py edits SS_RGB_SORTED_ATTR's line
+// and the SS_SORT_R instantiations in its copies of the source.
+#define SS_NODES_ATTR          // spectral broadcast and node eval
+#define SS_RAYS_ATTR           // per-ray spectral eval
+#define SS_RGB_ATTR            // RGB eval
+#define SS_SPEC_SAMPLE_ATTR    // LEAN spectral sample_direction
 #define SS_RGB_SORTED_ATTR
-#endif
-#ifndef SS_CONDUCTOR_ATTR    // occupancy of the FAST conductor caller (probe builds override it)
-#define SS_CONDUCTOR_ATTR __attribute__((amdgpu_waves_per_eu(4)))
-#endif
-#ifndef SS_SORT_R            // probe builds: the window of the wave-sorted RGB kernels
+#define SS_CONDUCTOR_ATTR __attribute__((amdgpu_waves_per_eu(4)))   // the FAST conductor caller
 #define SS_SORT_R 4
-#endif
 constexpr float kLog2e = 1.44269504088896340736f;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -549,10 +538,7 @@ __device__ __forceinline__ float render_sun_rgb_compact(const float* table, int 
 // rows (48 cycles: ds_read_b96 services 8 lanes per cycle).  Same Horner order per
 // channel as render_sun_rgb_compact (bitwise the same values).
 constexpr int kSunRowFloats = 20;
-#ifndef SS_SUN_ROWS_LDS   // probe builds: rows held in LDS (<= kSunRowsStaged; lanes past them read the table)
-#define SS_SUN_ROWS_LDS kSunRowsStaged
-#endif
-constexpr int kSunRowsLds = SS_SUN_ROWS_LDS;
+constexpr int kSunRowsLds = kSunRowsStaged;   // rows held in LDS (lanes past them read the table)
 static_assert(kSunRowsLds <= kSunRowsStaged, "LDS rows");
 struct SunRowsRgb {
     float4 r[kSunRowsLds][kNbSunCtrlPts][kSunRowFloats / 4];
@@ -4050,14 +4036,10 @@ SS_SAMPLE_DIRECTION_SPEC_LEAN(sunsky_sample_direction_spec_lean_ref, false)
 // LEAN spectral sample_direction at 4 wavelengths in wave-sorted windows of SS_SPEC_SORT_R x 64
 // samples (the C ABI's call when nlam == 4): bitwise the unsorted LEAN kernel
 // (test_spectral_sorted_kernel_bitwise_vs_unsorted)
-#ifndef SS_SPEC_SORT_R
 #define SS_SPEC_SORT_R 3
-#endif
 // 4 waves/SIMD (127 VGPRs, 2 spilled; 131 and 3 waves without): interleaved A/B against the
 // unsorted LEAN kernel 0.963 (3 waves: 1.027; R = 2: 0.999, at 4 waves 0.994), profiles/r03_v13_ab_spec_sorted.log
-#ifndef SS_SPEC_SORTED_ATTR
 #define SS_SPEC_SORTED_ATTR __attribute__((amdgpu_waves_per_eu(4)))
-#endif
 #define SS_SAMPLE_DIRECTION_SPEC4_SORTED(NAME, FAST, R)                                                       \
     extern "C" __global__ __launch_bounds__(SS_BLOCK) SS_SPEC_SORTED_ATTR void NAME(                           \
         const SunskyKArgs* __restrict__ Kp, const float* ux, const float* uy, const float* px, const float* py, const float* pz,   \
@@ -4170,14 +4152,10 @@ SS_SAMPLE_WAVELENGTHS(sunsky_sample_wavelengths_spec_ref, false, true)
         sample_ray_body<FAST, SPEC>(*Kp, wls, s2x, s2y, s3x, s3y, active, n, ox, oy, oz, dx, dy, dz, lam,        \
                                     lstride, weight, wstride);                                                 \
     }
-#ifndef SS_RAY_SORT_R
 #define SS_RAY_SORT_R 4
-#endif
 // 4 waves/SIMD (125 VGPRs; 131 and 3 waves without): interleaved A/B against the unsorted
 // kernel 0.922 (3 waves 0.976; R = 3: 0.946, at 4 waves 0.955), profiles/r03_v18_ab_sample_ray_sorted.log
-#ifndef SS_RAY_SORTED_ATTR
 #define SS_RAY_SORTED_ATTR __attribute__((amdgpu_waves_per_eu(4)))
-#endif
 #define SS_SAMPLE_RAY_RGB_SORTED(NAME, FAST, R)                                                               \
     extern "C" __global__ __launch_bounds__(SS_BLOCK) SS_RAY_SORTED_ATTR void NAME(                           \
         const SunskyKArgs* __restrict__ Kp, const float* wls, const float* s2x, const float* s2y, const float* s3x,                 \
@@ -4195,9 +4173,7 @@ SS_SAMPLE_RAY(sunsky_sample_ray_rgb_ref, false, false)
 SS_SAMPLE_RAY(sunsky_sample_ray_spec_fast, true, true)
 SS_SAMPLE_RAY(sunsky_sample_ray_spec_ref, false, true)
 
-#ifndef SS_DIFFUSE_SPEC_ATTR   // probe builds: occupancy of the FAST spectral diffuse caller
-#define SS_DIFFUSE_SPEC_ATTR
-#endif
+#define SS_DIFFUSE_SPEC_ATTR   // occupancy of the FAST spectral diffuse caller: the compiler's choice
 #define SS_DIRECT_DIFFUSE(NAME, FAST, SPEC, ATTR)                                                             \
     extern "C" __global__ __launch_bounds__(SS_BLOCK) ATTR void NAME(                                         \
         const SunskyKArgs* __restrict__ Kp, const float* nx, const float* ny, const float* nz, const float* rho, const float* lam, \
@@ -4262,9 +4238,7 @@ extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_eval_vjp_rgb(
     size_t n, const float* dout, size_t ostride, float sign, float* partials) {
     eval_vjp_rgb_body(*Kp, vjp, wx, wy, wz, active, n, dout, ostride, sign, partials);
 }
-#ifndef SS_VJP_SPEC_ATTR
 #define SS_VJP_SPEC_ATTR
-#endif
 extern "C" __global__ __launch_bounds__(SS_BLOCK) SS_VJP_SPEC_ATTR void sunsky_eval_vjp_spec(
     const SunskyKArgs* __restrict__ Kp, const float* vjp, const float* wx, const float* wy, const float* wz, const float* lam,
     size_t lstride, int nlam, const uint8_t* active, size_t n, const float* dout, size_t ostride, float sign,
@@ -4339,2024 +4313,12 @@ extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_eval_vjp_dir_spec(
 SS_BAKE(sunsky_bake_latlong_rgb_fast, sunsky_bake_latlong_spec_fast, true)
 SS_BAKE(sunsky_bake_latlong_rgb_ref, sunsky_bake_latlong_spec_ref, false)
 
-// ======================================================================
-// Device staging of parameters_changed (sunsky.cpp:242-285): the radiance tables
-// (compute_radiance_params, sunsky.h:158-231; compute_sun_params, :404-419) and the
-// JIT sampling weight / wavelength distribution (estimate_sky_sun_ratio,
-// sunsky.cpp:772-886) written straight into the emitter's device state, on the
-// caller's stream.  The host writes the rest of the state (geometry, TGMM) with an
-// async copy just before; launches that follow on the stream see the new state.
-// ======================================================================
-// One workgroup: every sky coefficient / radiance entry, every sun-table entry, then
-// one thread per channel folds it (sunsky_staging.h: the host model's arithmetic).
-extern "C" __global__ __launch_bounds__(256) void sunsky_stage_radiance(StageArgs A) {
-    __shared__ float p[kNbWavelengths * kNbSkyParams];
-    __shared__ float r[kNbWavelengths];
-    const int t = threadIdx.x;
-    const int np = A.nch * kNbSkyParams;
-    for (int e = t; e < np; e += blockDim.x)
-        p[e] = radiance_param(A.sky_params_ds, np, e, A.rs, A.albedo[e / kNbSkyParams]);
-    for (int e = t; e < A.nch; e += blockDim.x) r[e] = radiance_param(A.sky_rad_ds, A.nch, e, A.rs, A.albedo[e]);
-    for (int i = t; i < A.sun_block; i += blockDim.x) A.sun_table[i] = sun_param(A.sun_rad_ds, A.sun_block, i, A.rs);
-    __syncthreads();
-    if (t < A.nch) {
-        SkyChannel ch;
-        FastChannel f;
-        fold_channel(&p[t * kNbSkyParams], r[t], A.variant, A.sky_scale, &ch, &f);
-        A.state->sky[t] = ch;
-        A.state->fsky[t] = f;
-    }
-}
-
-// Tangent tables of eval_jvp / eval_vjp (sunsky_staging.h TangentArgs): one float per
-// thread, fp64 Bezier derivatives of the device-resident datasets, the same code as the
-// host model's eval_tangent.
-extern "C" __global__ __launch_bounds__(256) void sunsky_stage_tangent(TangentArgs A) {
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < A.total; idx += gridDim.x * blockDim.x)
-        A.out[idx] = tangent_buffer_value(A, idx);
-}
-
-// Workgroup j = quadrature row j, thread i = point (i, j): its direction terms once,
-// every channel's sky and sun terms, then a fixed-shape tree reduction over the row's
-// points in LDS (deterministic: the same order on every run).
-extern "C" __global__ __launch_bounds__(kQuadBlock) void sunsky_stage_quad_points(QuadArgs A) {
-    __shared__ float red[2 * kNbWavelengths][kQuadBlock];
-    const int j = blockIdx.x, i = threadIdx.x;
-    const SunskyKArgs& K = *A.state;
-    float as[kNbWavelengths], au[kNbWavelengths];
-#pragma unroll
-    for (int c = 0; c < kNbWavelengths; ++c) as[c] = au[c] = 0.f;
-    if (i < A.nq) {
-        const QuadDir d = quad_dir(K, A.qx, A.qw, i, j);
-        const float wj = A.qw[j];
-#pragma unroll
-        for (int c = 0; c < kNbWavelengths; ++c)
-            if (c < A.nch) quad_channel(K, K.sun_table, K.sun_ld, d, wj, c, &as[c], &au[c]);
-    }
-#pragma unroll
-    for (int c = 0; c < kNbWavelengths; ++c) {
-        red[c][i] = as[c];
-        red[kNbWavelengths + c][i] = au[c];
-    }
-    __syncthreads();
-    for (int h = kQuadBlock / 2; h > 0; h >>= 1) {
-        if (i < h)
-#pragma unroll
-            for (int c = 0; c < 2 * kNbWavelengths; ++c) red[c][i] += red[c][i + h];
-        __syncthreads();
-    }
-    if (i < A.nch) {
-        A.rows[(size_t)j * A.nch + i] = red[i][0];
-        A.rows[(size_t)(A.nq + j) * A.nch + i] = red[kNbWavelengths + i][0];
-    }
-}
-
-// One workgroup: the row sums to LDS, thread c adds channel c's rows in row order, then
-// one thread derives the sampling weight and the wavelength distribution (quad_finish).
-extern "C" __global__ __launch_bounds__(256) void sunsky_stage_quad_finish(QuadArgs A) {
-    __shared__ float rows[2 * 200 * kNbWavelengths];
-    __shared__ float sky[kNbWavelengths], sun[kNbWavelengths];
-    const int total = 2 * A.nq * A.nch;
-    for (int i = threadIdx.x; i < total; i += blockDim.x) rows[i] = A.rows[i];
-    __syncthreads();
-    const int c = threadIdx.x;
-    if (c < A.nch) {
-        float s = 0.f, u = 0.f;
-        for (int j = 0; j < A.nq; ++j) {
-            s += rows[j * A.nch + c];
-            u += rows[(A.nq + j) * A.nch + c];
-        }
-        sky[c] = s;
-        sun[c] = u;
-    }
-    __syncthreads();
-    if (c == 0) {
-        const bool ok = quad_finish(A.state, sky, sun, A.cie_y, A.sky_scale, A.sun_scale);
-        if (!ok) *A.status = 1;   // sticky until the host reads it back (sync_host)
-    }
-}
-
-// ======================================================================
-// Frame sequences (sunsky_sequence): out = sum_k w_k eval_k(wi) over K frames of one emitter
-// that differ in sun direction and turbidity, in one launch.  A lane reads its direction once,
-// forms the frame-independent terms once (wo, cos theta, r = 1 / (cos theta + 0.01),
-// sqrt(cos theta)), then walks the frame records (SeqFrame, sunsky_kernel_args.h) with one
-// address per wave: the records are read through the constant address space, so a frame's
-// sun vector, weight and channel coefficients arrive by scalar loads into SGPRs, the next
-// frame's issued before this frame's arithmetic.  Per frame the chord, gamma and cos gamma are
-// dir_terms' arithmetic and the sky values sky_fast / sky_ref's, added as fma(w_k, v, acc) in
-// frame order into fp32 accumulators; one non-temporal store per plane at the end.  The work
-// is transcendental issue with next to no memory traffic.
-// A lane inside frame k's disc takes a rare branch: the segment from the full threshold table,
-// the disc coordinates by sun_disc64's arithmetic with the frame's sun vector, and the few
-// sun-table entries it needs lerped on the spot from the raw dataset with the frame's
-// turbidity scalars (sun_param: the bits of a single emitter's staged table), so a frame
-// carries no sun table.  The branch reads the state and the record through opaque handles:
-// none of its loads is hoisted into the frame loop.
-// ======================================================================
-typedef const __attribute__((address_space(4))) float* seq_cfloat_p;
-typedef const __attribute__((address_space(4))) int* seq_cint_p;
-
-constexpr int kSeqHeaderFloats = (int)(kSeqFrameHeader / 4);
-constexpr int kSeqChanFloats = (int)((sizeof(FastChannel) + sizeof(SkyChannel)) / 4);
-
-// record k of a sequence with nch channels, as floats in the constant address space
-__device__ __forceinline__ seq_cfloat_p seq_record(const void* frames, int nch, int k) {
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wold-style-cast"
-    return (seq_cfloat_p)frames + (size_t)k * (size_t)(kSeqHeaderFloats + nch * kSeqChanFloats);
-#pragma clang diagnostic pop
-}
-
-template <bool FAST>
-__device__ __forceinline__ typename ChanSel<FAST>::T seq_chan(seq_cfloat_p rec, int nch, int c) {
-    if constexpr (FAST) {
-        seq_cfloat_p p = rec + kSeqHeaderFloats + c * 12;
-        FastChannel f;
-        f.A = p[0]; f.Bl2 = p[1]; f.El2 = p[2]; f.P = p[3]; f.Q = p[4];
-        f.Cs = p[5]; f.Ds = p[6]; f.Fs = p[7]; f.Gs = p[8]; f.Hs = p[9];
-        f.pad[0] = f.pad[1] = 0.f;
-        return f;
-    } else {
-        seq_cfloat_p p = rec + kSeqHeaderFloats + nch * 12 + c * 16;
-        SkyChannel s;
-        s.A = p[0]; s.B = p[1]; s.C = p[2]; s.D = p[3]; s.E = p[4]; s.F = p[5]; s.G = p[6]; s.H = p[7]; s.I = p[8];
-        s.P = p[9]; s.rad = p[10]; s.Bl2 = p[11]; s.El2 = p[12]; s.Q = p[13];
-        s.pad[0] = s.pad[1] = 0.f;
-        return s;
-    }
-}
-
-// What the frame loop reads of one record: N channels starting at channel list c[]
-template <bool FAST, int N>
-struct SeqHot {
-    float3_ sn;
-    float w;
-    typename ChanSel<FAST>::T ch[N];
-};
-
-template <bool FAST, int N>
-__device__ __forceinline__ SeqHot<FAST, N> seq_load(const void* frames, int nch, int k, const int (&c)[N]) {
-    seq_cfloat_p rec = seq_record(frames, nch, k);
-    SeqHot<FAST, N> h;
-    h.sn = mk3(rec[0], rec[1], rec[2]);
-    h.w = rec[3];
-#pragma unroll
-    for (int i = 0; i < N; ++i) h.ch[i] = seq_chan<FAST>(rec, nch, c[i]);
-    return h;
-}
-
-// The frame-independent part of dir_terms
-struct SeqDir {
-    float3_ wo;
-    float r, sq;
-    bool active;
-};
-
-template <bool FAST>
-__device__ __forceinline__ SeqDir seq_dir(float3_ wo, bool mask) {
-    SeqDir s;
-    s.wo = wo;
-    if (FAST) {
-        s.r = fast_rcp(wo.z + 0.01f);
-        s.sq = fast_sqrt(wo.z);   // NaN below the horizon: those lanes store 0
-    } else {
-        s.r = 1.f / (wo.z + 0.01f);
-        s.sq = safe_sqrtf_(wo.z);
-    }
-    s.active = mask && (wo.z >= 0.f);
-    return s;
-}
-
-// dir_terms' per-sun part for frame sun vector sn: the same statements, so a frame's terms are
-// the bits its single emitter computes (the disc test included)
-template <bool FAST>
-__device__ __forceinline__ DirTerms seq_frame_terms(const SeqDir& s, float3_ sn, float cos_cutoff) {
-    DirTerms t;
-    const float3_ wo = s.wo;
-    t.cos_theta = wo.z;
-    float d = dot3(sn, wo);
-    const float sg = signbit(d) ? -1.f : 1.f;
-    float3_ v = mk3(fmaf(-sg, sn.x, wo.x), fmaf(-sg, sn.y, wo.y), fmaf(-sg, sn.z, wo.z));
-    float h = 0.5f * (FAST ? fast_sqrt(dot3(v, v)) : sqrtf(dot3(v, v)));
-    t.h = h;
-    t.wx = wo.x;
-    t.wy = wo.y;
-    float temp = 2.f * (FAST ? asin_half_chord(h) : asinf(h));
-    t.gamma = d >= 0.f ? temp : kPi - temp;
-    if (FAST) {
-        float c = fmaf(h * h, -2.f, 1.f);
-        t.cg = d >= 0.f ? c : -c;
-    } else {
-        t.cg = cosf(t.gamma);
-    }
-    t.r = s.r;
-    t.sq = s.sq;
-    t.cg2 = t.cg * t.cg;
-    t.u = 1.f + t.cg2;
-    t.active = s.active;
-    t.hit_sun = t.active && (d >= cos_cutoff);
-    t.sun_pos = 0;
-    t.sun_x = t.sun_cpsi = 0.f;
-    return t;
-}
-
-// An index the compiler cannot see through (opaque_kargs' idiom for the record pointer)
-__device__ __forceinline__ int seq_opaque(int k) {
-    asm volatile("" : "+s"(k));
-    return k;
-}
-
-// The turbidity lerp scalars of a record, for sun_param
-__device__ __forceinline__ RadianceStage seq_sun_stage(seq_cfloat_p rec) {
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wold-style-cast"
-    seq_cint_p ri = (seq_cint_p)rec;
-#pragma clang diagnostic pop
-    RadianceStage rs;
-    rs.x = 0.f;
-    rs.t_rem = rec[4];
-    rs.t_low = ri[5];
-    rs.t_high = ri[6];
-    rs.in_range = 1;
-    return rs;
-}
-
-// sun_segment_index over the whole threshold table: it counts the thresholds a cos theta
-// passes, so the index is the one an emitter's [sun_row_lo, sun_row_hi] window gives
-__device__ __forceinline__ int seq_segment_index(const SunskyKArgs& K, float cos_theta) {
-    int pos = 0;
-#pragma unroll 1
-    for (int j = 1; j < kNbSunSegments; ++j) pos += cos_theta >= K.sun_seg_z[j] ? 1 : 0;
-    return pos;
-}
-
-// sun_disc64 with the frame's sun vector
-__device__ __forceinline__ SunDisc64 seq_sun_disc64(const SunskyKArgs& K, float3_ sn, float wx, float wy,
-                                                    float cos_theta) {
-    SunDisc64 d;
-    d.pos = seq_segment_index(K, cos_theta);
-    const double frac = (double)d.pos * (1.0 / (double)kNbSunSegments);
-    d.x = (double)elevation_fast(cos_theta) - 1.5707963267948966 * (frac * frac * frac);
-    const double vx = (double)wx - (double)sn.x, vy = (double)wy - (double)sn.y, vz = (double)cos_theta - (double)sn.z;
-    const double v2 = fma(vz, vz, fma(vy, vy, vx * vx));
-    const double inv = (double)K.cpsi_inv_hi + (double)K.cpsi_inv_lo;
-    d.cpsi = sqrt(fmax(fma(-inv, v2 * fma(-0.25, v2, 1.0), 1.0), 0.0));
-    return d;
-}
-
-// The reference kernels' segment and x (sun_segment_ref)
-__device__ __forceinline__ int seq_segment_ref(const SunskyKArgs& K, float cos_theta, float* x) {
-    const int pos = seq_segment_index(K, cos_theta);
-    const float elevation = kHalfPi - acosf(cos_theta);
-    const float frac = (float)pos / (float)kNbSunSegments;
-    *x = elevation - kHalfPi * (frac * frac * frac);
-    return pos;
-}
-
-// The reference-precision disc term from its coordinates (segment pos, elevation xs within it,
-// cos psi): what seq_disc_rgb<false> / seq_disc_spec<false> add for a direction, and what the
-// irradiance flux rule evaluates at its nodes with cos psi given (sunsky_sequence_irradiance_flux)
-__device__ __forceinline__ void seq_disc_rgb_at(const SunskyKArgs& Kf, const float* ds, int block, const RadianceStage& rs,
-                                                int pos, float xs, float cpsi, float v[3]) {
-    constexpr int per_c = kNbSunCtrlPts * kNbSunLdParams;
-    const float conv = (float)kSpecToRgbSunConv;
-#pragma unroll 1
-    for (int c = 0; c < 3; ++c) {
-        float s[per_c];
-#pragma unroll
-        for (int e = 0; e < per_c; ++e) s[e] = sun_param(ds, block, pos * (3 * per_c) + c * per_c + e, rs);
-        v[c] += Kf.sun_scale * render_sun_rgb(s, 0, 0, xs, cpsi) * Kf.area_ratio * conv;
-    }
-}
-
-// sun_spec_term<false>: render_sun_spec x sun_limb_darkening for the channel pair (lo, lo + 1, f)
-__device__ __forceinline__ float seq_disc_spec_at(const SunskyKArgs& Kf, const float* ds, int block,
-                                                  const RadianceStage& rs, int pos, float xs, float cpsi, int lo, float f,
-                                                  float o) {
-    const int hi = lo + 1;
-    auto poly = [&](int c) {
-        const int q = (pos * kNbWavelengths + c) * kNbSunCtrlPts;
-        float res = 0.f;
-#pragma unroll
-        for (int e = 0; e < kNbSunCtrlPts; ++e) res += powif_(xs, e) * sun_param(ds, block, q + e, rs);
-        return res;
-    };
-    const float sa = poly(lo);
-    float sun = sa;
-    if (f != 0.f) sun = lerpf_(sa, hi < kNbWavelengths ? poly(hi) : 0.f, f);
-    const float ld = sun_limb_darkening(Kf.sun_ld, lo, hi, f, cpsi);
-    return o + Kf.sun_scale * sun * ld * Kf.area_ratio;
-}
-
-// RGB disc term of frame k added to the lane's 3 sky values (the rare branch)
-template <bool FAST>
-__device__ __forceinline__ void seq_disc_rgb(const SunskyKArgs& K, const SeqArgs& A, int k, const DirTerms& t,
-                                             float v[3]) {
-    const SunskyKArgs& Kf = opaque_kargs(K);
-    seq_cfloat_p rec = seq_record(A.frames, 3, seq_opaque(k));
-    const RadianceStage rs = seq_sun_stage(rec);
-    const float* ds = A.sun_rad_ds;
-    const int block = A.sun_block;
-    constexpr int per_c = kNbSunCtrlPts * kNbSunLdParams;
-    if constexpr (FAST) {
-        const SunDisc64 d = seq_sun_disc64(Kf, mk3(rec[0], rec[1], rec[2]), t.wx, t.wy, t.cos_theta);
-#pragma unroll 1
-        for (int c = 0; c < 3; ++c) {   // add_sun_rgb64's Horner forms
-            const int base = d.pos * (3 * per_c) + c * per_c;
-            double res = 0.0;
-#pragma unroll 1
-            for (int q = kNbSunCtrlPts - 1; q >= 0; --q) {
-                const int r = base + q * kNbSunLdParams;
-                double inner = (double)sun_param(ds, block, r + kNbSunLdParams - 1, rs);
-#pragma unroll
-                for (int j = kNbSunLdParams - 2; j >= 0; --j) inner = fma(inner, d.cpsi, (double)sun_param(ds, block, r + j, rs));
-                res = fma(res, d.x, inner);
-            }
-            v[c] = (float)fma((double)Kf.sun_mul, res, (double)v[c]);
-        }
-    } else {
-        float xs;
-        const int pos = seq_segment_ref(Kf, t.cos_theta, &xs);
-        seq_disc_rgb_at(Kf, ds, block, rs, pos, xs, cos_psi(t.gamma, Kf.inv_sin2_half_ap), v);
-    }
-}
-
-// Spectral disc term of frame k for the channel pair (lo, lo + 1, f) added to the sky value o
-template <bool FAST>
-__device__ __forceinline__ float seq_disc_spec(const SunskyKArgs& K, const SeqArgs& A, int k, const DirTerms& t,
-                                               int lo, float f, float o) {
-    const SunskyKArgs& Kf = opaque_kargs(K);
-    seq_cfloat_p rec = seq_record(A.frames, kNbWavelengths, seq_opaque(k));
-    const RadianceStage rs = seq_sun_stage(rec);
-    const float* ds = A.sun_rad_ds;
-    const int block = A.sun_block;
-    const int hi = lo + 1;
-    if constexpr (FAST) {   // add_sun_spec64
-        const SunDisc64 d = seq_sun_disc64(Kf, mk3(rec[0], rec[1], rec[2]), t.wx, t.wy, t.cos_theta);
-        const double fd = (double)f;
-        auto poly = [&](int c) {
-            const int q = (d.pos * kNbWavelengths + c) * kNbSunCtrlPts;
-            return fma(fma(fma((double)sun_param(ds, block, q + 3, rs), d.x, (double)sun_param(ds, block, q + 2, rs)), d.x,
-                           (double)sun_param(ds, block, q + 1, rs)), d.x, (double)sun_param(ds, block, q, rs));
-        };
-        double sun = poly(lo);
-        if (f != 0.f) sun = fma(fd, (hi < kNbWavelengths ? poly(hi) : 0.0) - sun, sun);
-        double ld = 0.0;
-#pragma unroll 1
-        for (int j = kNbSunLdParams - 1; j >= 0; --j) {
-            double coef = (double)Kf.sun_ld[lo * kNbSunLdParams + j];
-            if (f != 0.f) coef = fma(fd, (hi < kNbWavelengths ? (double)Kf.sun_ld[hi * kNbSunLdParams + j] : 0.0) - coef, coef);
-            ld = fma(ld, d.cpsi, coef);
-        }
-        return (float)fma((double)Kf.sun_mul, sun * ld, (double)o);
-    } else {
-        float xs;
-        const int pos = seq_segment_ref(Kf, t.cos_theta, &xs);
-        return seq_disc_spec_at(Kf, ds, block, rs, pos, xs, cos_psi(t.gamma, Kf.inv_sin2_half_ap), lo, f, o);
-    }
-}
-
-// Direction sources: a ray batch (eval: wo = -wi) or the lat-long grid of bake_latlong
-struct SeqRays {
-    const float *wx, *wy, *wz;
-    const uint8_t* active;
-    __device__ __forceinline__ float3_ local_dir(const SunskyKArgs& K, size_t i, bool* m) const {
-        *m = !active || active[i] != 0;
-        return to_local(K, flip3<true>(wx[i], wy[i], wz[i]));
-    }
-};
-struct SeqGrid {
-    LatLong G;
-    __device__ __forceinline__ float3_ local_dir(const SunskyKArgs& K, size_t i, bool* m) const {
-        *m = true;
-        return to_local(K, latlong_dir(G, i));
-    }
-};
-
-template <bool FAST, class SRC>
-__device__ __forceinline__ void seq_rgb_body(const SunskyKArgs& K, const SeqArgs& A, const SRC& src, size_t n,
-                                             float* __restrict__ out, size_t ostride) {
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    const int chans[3] = {0, 1, 2};
-    const int count = A.count;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        bool m;
-        const float3_ wo = src.local_dir(K, i, &m);
-        const SeqDir s = seq_dir<FAST>(wo, m);
-        float acc[3] = {0.f, 0.f, 0.f};
-        SeqHot<FAST, 3> cur = seq_load<FAST, 3>(A.frames, 3, 0, chans);
-#pragma unroll 1
-        for (int k = 0; k < count; ++k) {
-            // the next record's scalar loads, in flight under this frame's arithmetic
-            const SeqHot<FAST, 3> nxt = seq_load<FAST, 3>(A.frames, 3, k + 1 < count ? k + 1 : k, chans);
-            const DirTerms t = seq_frame_terms<FAST>(s, cur.sn, K.cos_cutoff);
-            float v[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) v[c] = sky_eval<FAST>(cur.ch[c], t, K.sky_scale);
-            if (t.hit_sun) seq_disc_rgb<FAST>(K, A, k, t, v);
-            if constexpr (!FAST) {
-                const float cie = (float)kCieYNormalization;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) v[c] = v[c] * cie;
-            }
-#pragma unroll
-            for (int c = 0; c < 3; ++c) acc[c] = fmaf(cur.w, v[c], acc[c]);
-            cur = nxt;
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) store_nt(s.active ? acc[c] : 0.f, out + (size_t)c * ostride + i);
-    }
-}
-
-// Spectral, one broadcast wavelength list: per output wavelength the frame loop over its
-// channel pair (the disc term is not linear in the nodes, so nothing is shared between
-// wavelengths but the direction's frame-independent terms)
-template <bool FAST, class SRC>
-__device__ __forceinline__ void seq_spec_body(const SunskyKArgs& K, const SeqArgs& A, const LambdaSet& L,
-                                              const SRC& src, size_t n, float* __restrict__ out, size_t ostride) {
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    const int count = A.count;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        bool m;
-        const float3_ wo = src.local_dir(K, i, &m);
-        const SeqDir s = seq_dir<FAST>(wo, m);
-#pragma unroll 1
-        for (int q = 0; q < L.m; ++q) {
-            const int lo = L.lo[q];
-            const float f = L.f[q];
-            float acc = 0.f;
-            if (f >= 0.f) {
-                const int chans[2] = {lo, lo + 1 < kNbWavelengths ? lo + 1 : lo};
-                SeqHot<FAST, 2> cur = seq_load<FAST, 2>(A.frames, kNbWavelengths, 0, chans);
-#pragma unroll 1
-                for (int k = 0; k < count; ++k) {
-                    const SeqHot<FAST, 2> nxt =
-                        seq_load<FAST, 2>(A.frames, kNbWavelengths, k + 1 < count ? k + 1 : k, chans);
-                    const DirTerms t = seq_frame_terms<FAST>(s, cur.sn, K.cos_cutoff);
-                    float v = sky_eval<FAST>(cur.ch[0], t, K.sky_scale);
-                    if (f != 0.f) v = lerpf_(v, sky_eval<FAST>(cur.ch[1], t, K.sky_scale), f);
-                    if (t.hit_sun) v = seq_disc_spec<FAST>(K, A, k, t, lo, f, v);
-                    acc = fmaf(cur.w, v, acc);
-                    cur = nxt;
-                }
-            }
-            store_nt(f >= 0.f && s.active ? acc : 0.f, out + (size_t)q * ostride + i);
-        }
-    }
-}
-
-#define SS_SEQUENCE(SUFFIX, FAST)                                                                              \
-    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_eval_rgb##SUFFIX(                   \
-        const SunskyKArgs* __restrict__ Kp, SeqArgs A, const float* wx, const float* wy, const float* wz,      \
-        const uint8_t* active, size_t n, float* out, size_t ostride) {                                         \
-        seq_rgb_body<FAST>(*Kp, A, SeqRays{wx, wy, wz, active}, n, out, ostride);                              \
-    }                                                                                                          \
-    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_eval_spec##SUFFIX(                  \
-        const SunskyKArgs* __restrict__ Kp, SeqArgs A, LambdaSet L, const float* wx, const float* wy,          \
-        const float* wz, const uint8_t* active, size_t n, float* out, size_t ostride) {                        \
-        seq_spec_body<FAST>(*Kp, A, L, SeqRays{wx, wy, wz, active}, n, out, ostride);                          \
-    }                                                                                                          \
-    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_bake_rgb##SUFFIX(                   \
-        const SunskyKArgs* __restrict__ Kp, SeqArgs A, LatLong G, float* out, size_t ostride) {                \
-        seq_rgb_body<FAST>(*Kp, A, SeqGrid{G}, (size_t)G.w * (size_t)G.h, out, ostride);                       \
-    }                                                                                                          \
-    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_bake_spec##SUFFIX(                  \
-        const SunskyKArgs* __restrict__ Kp, SeqArgs A, LatLong G, LambdaSet L, float* out, size_t ostride) {   \
-        seq_spec_body<FAST>(*Kp, A, L, SeqGrid{G}, (size_t)G.w * (size_t)G.h, out, ostride);                   \
-    }
-SS_SEQUENCE(_fast, true)
-SS_SEQUENCE(_ref, false)
-
-// ======================================================================
-// Reverse mode over a sequence (sunsky_sequence_eval_vjp): with the cotangent d_out,
-//   grad_weight[k]    += sum_rays sum_planes d_out eval_k
-//   grad_turbidity[k] += w_k sum_rays sum_planes d_out d eval_k / d T_k
-//   grad_sun_dir[3 k + a] += w_k sum_rays sum_planes d_out d eval_k / d s_k[a]
-// in reference-precision arithmetic whatever the sequence's precision (eval_vjp's conventions:
-// masks, segments and floor(T) are not differentiated).  One ray per lane in a grid-stride loop
-// whose trip count is uniform per workgroup; the direction's frame-independent terms once, then
-// the frame loop of seq_rgb_body.  Per frame the terms are the single emitter's (sky_val,
-// sky_tan_weights, sky_dot, sky_tan_gamma, unit_angle_tan_*, cos_psi_jvp, the disc polynomial
-// and its derivatives) against the frame's gradient record (SeqGradFrame), both read through
-// the constant address space with one address per wave; the next frame's header and sun
-// tangents are loaded under this frame's arithmetic, a channel's two 10-float tangent rows
-// where the channel is evaluated (two frames' rows would not fit the scalar registers).
-// Every frame needs its own 5 sums over rays.  A lane folds d eta x (unit-elevation sum) into
-// its 3 sun sums and scales by w_k; the wave adds the 5 values by shuffles (wave_sum); lane 0
-// adds them to the wave's row [count][5], kept in dynamic LDS while count <= kSeqGradLdsFrames
-// (the workgroup then adds its 4 rows in wave order into one row of the workspace at the end),
-// otherwise kept in the workspace itself, one row per wave (the first trip stores, later trips
-// add: no row is ever cleared).  sunsky_sequence_grad_reduce adds the rows in a fixed order.  No float atomics: two runs give the same bits.
-// ======================================================================
-__device__ __forceinline__ seq_cfloat_p seq_grad_record(const void* grads, int nch, int k) {
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wold-style-cast"
-    return (seq_cfloat_p)grads + (size_t)k * (size_t)(2 * seq_grad_block(nch) + 12);
-#pragma clang diagnostic pop
-}
-
-// What the frame loop prefetches of a frame: the record's header and the gradient record's sun tangents
-struct SeqGradHot {
-    float3_ sn;
-    float w;
-    float3_ dl[3];
-    float deta[3];
-};
-
-__device__ __forceinline__ SeqGradHot seq_grad_load(const void* frames, const void* grads, int nch, int k) {
-    seq_cfloat_p rec = seq_record(frames, nch, k);
-    seq_cfloat_p g = seq_grad_record(grads, nch, k) + 2 * seq_grad_block(nch);
-    SeqGradHot h;
-    h.sn = mk3(rec[0], rec[1], rec[2]);
-    h.w = rec[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        h.dl[a] = mk3(g[3 * a], g[3 * a + 1], g[3 * a + 2]);
-        h.deta[a] = g[9 + a];
-    }
-    return h;
-}
-
-// One sky channel's value and reverse-mode terms (sky_side without the albedo tangent): the
-// unscaled value, the tangents along turbidity and the unit elevation (d gamma = 0), and the
-// gamma part of the sun axes
-struct SeqSkySide { float v, t, e, gm; };
-
-__device__ __forceinline__ SeqSkySide seq_sky_side(const SkyChannel& k, seq_cfloat_p dT, seq_cfloat_p dE,
-                                                   const DirTerms& t, float sg) {
-    const SkyVal s = sky_val(k, t);
-    const SkyTanW W = sky_tan_weights(k, t, s);
-    float a[10], b[10];
-#pragma unroll
-    for (int p = 0; p < 10; ++p) { a[p] = dT[p]; b[p] = dE[p]; }
-    SeqSkySide r;
-    r.v = W.w[9] * k.rad;
-    r.t = sky_dot(W, a);
-    r.e = sky_dot(W, b);
-    r.gm = sky_tan_gamma(k, t, s, sg);
-    return r;
-}
-
-// RGB disc terms of frame k (the rare branch; seq_disc_rgb<false>'s value, eval_vjp_rgb_body's
-// derivatives): the turbidity slope of each table entry on the spot from the raw dataset
-// (sun_param_tangent with dT = 1), d cos psi along the 3 sun axes.  g: w, T, s_x, s_y, s_z.
-__device__ __forceinline__ void seq_disc_vjp_rgb(const SunskyKArgs& K, const SeqArgs& A, int k, const DirTerms& t,
-                                                 float sg, const float dgs[3], const float cot[3],
-                                                 float g[kSeqGradSums]) {
-    const SunskyKArgs& Kf = opaque_kargs(K);
-    seq_cfloat_p rec = seq_record(A.frames, 3, seq_opaque(k));
-    const RadianceStage rs = seq_sun_stage(rec);
-    TangentStage ts{};
-    ts.dT = 1.0;
-    ts.t_low = rs.t_low;
-    ts.t_high = rs.t_high;
-    const float* ds = A.sun_rad_ds;
-    const int block = A.sun_block;
-    constexpr int per_c = kNbSunCtrlPts * kNbSunLdParams;
-    float xs, cp = 0.f, dcps[3];
-    const int pos = seq_segment_ref(Kf, t.cos_theta, &xs);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) cos_psi_jvp(Kf, t, sg, dgs[a], &cp, &dcps[a]);
-    const float sc = Kf.sun_scale * Kf.area_ratio * (float)kSpecToRgbSunConv;
-#pragma unroll 1
-    for (int c = 0; c < 3; ++c) {
-        const int base = pos * (3 * per_c) + c * per_c;
-        float v = 0.f, dT = 0.f, dC = 0.f;   // value, d / dT, d / d cos psi
-#pragma unroll 1
-        for (int kk = 0; kk < kNbSunCtrlPts; ++kk)
-#pragma unroll 1
-            for (int j = 0; j < kNbSunLdParams; ++j) {
-                const int e = base + kk * kNbSunLdParams + j;
-                const float S = sun_param(ds, block, e, rs), dS = sun_param_tangent(ds, block, e, ts);
-                const float xk = powif_(xs, kk);
-                v += xk * powif_(cp, j) * S;
-                dT += xk * powif_(cp, j) * dS;
-                if (j > 0) dC += xk * (float)j * powif_(cp, j - 1) * S;
-            }
-        const float cs = cot[c] * sc;
-        g[0] += cs * v;
-        g[1] += cs * dT;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) g[2 + a] += cs * dC * dcps[a];
-    }
-}
-
-// Spectral disc terms of frame k for the channel pair (lo, lo + 1, f) and cotangent cot
-__device__ __forceinline__ void seq_disc_vjp_spec(const SunskyKArgs& K, const SeqArgs& A, int k, const DirTerms& t,
-                                                  float sg, const float dgs[3], int lo, float f, float cot,
-                                                  float g[kSeqGradSums]) {
-    const SunskyKArgs& Kf = opaque_kargs(K);
-    seq_cfloat_p rec = seq_record(A.frames, kNbWavelengths, seq_opaque(k));
-    const RadianceStage rs = seq_sun_stage(rec);
-    TangentStage ts{};
-    ts.dT = 1.0;
-    ts.t_low = rs.t_low;
-    ts.t_high = rs.t_high;
-    const float* ds = A.sun_rad_ds;
-    const int block = A.sun_block;
-    const int hi = lo + 1;
-    float xs, cp = 0.f, dcps[3];
-    const int pos = seq_segment_ref(Kf, t.cos_theta, &xs);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) cos_psi_jvp(Kf, t, sg, dgs[a], &cp, &dcps[a]);
-    auto poly = [&](int c, float* d) {
-        const int q = (pos * kNbWavelengths + c) * kNbSunCtrlPts;
-        float res = 0.f, dres = 0.f;
-#pragma unroll
-        for (int e = 0; e < kNbSunCtrlPts; ++e) {
-            res += powif_(xs, e) * sun_param(ds, block, q + e, rs);
-            dres += powif_(xs, e) * sun_param_tangent(ds, block, q + e, ts);
-        }
-        *d = dres;
-        return res;
-    };
-    float dsun;
-    float sun = poly(lo, &dsun);
-    if (f != 0.f) {
-        float dsb = 0.f;
-        const float sb = hi < kNbWavelengths ? poly(hi, &dsb) : 0.f;
-        sun = lerpf_(sun, sb, f);
-        dsun = lerpf_(dsun, dsb, f);
-    }
-    const float ld = sun_limb_darkening(Kf.sun_ld, lo, hi, f, cp);
-    float dldc = 0.f;
-#pragma unroll 1
-    for (int j = 1; j < kNbSunLdParams; ++j) {
-        const float a = Kf.sun_ld[lo * kNbSunLdParams + j];
-        float coef = a;
-        if (f != 0.f) coef = lerpf_(a, hi < kNbWavelengths ? Kf.sun_ld[hi * kNbSunLdParams + j] : 0.f, f);
-        dldc += (float)j * powif_(cp, j - 1) * coef;
-    }
-    const float cs = cot * Kf.sun_scale * Kf.area_ratio;
-    g[0] += cs * sun * ld;
-    g[1] += cs * dsun * ld;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) g[2 + a] += cs * sun * dldc * dcps[a];
-}
-
-// A lane's 5 sums of frame k: the unit-elevation sum folded into the sun axes, the weight on
-// the parameter sums, inactive lanes 0; then the wave's sums into its row (lane 0).
-__device__ __forceinline__ void seq_grad_accumulate(float g[kSeqGradSums], float ge, const SeqGradHot& h, bool lane_active,
-                                                    float* row, int k, bool first) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) g[2 + a] = fmaf(h.deta[a], ge, g[2 + a]);
-#pragma unroll
-    for (int p = 1; p < kSeqGradSums; ++p) g[p] *= h.w;
-    float w[kSeqGradSums];
-#pragma unroll
-    for (int p = 0; p < kSeqGradSums; ++p) w[p] = wave_sum(lane_active ? g[p] : 0.f);
-    if ((threadIdx.x & 63) == 0) {
-        float* r = row + (size_t)k * kSeqGradSums;
-#pragma unroll
-        for (int p = 0; p < kSeqGradSums; ++p) r[p] = first ? w[p] : r[p] + w[p];
-    }
-}
-
-// The rows of a workgroup's waves: dynamic LDS (4 x count x 5 floats) or the workspace
-extern __shared__ float seq_grad_lds[];
-
-__device__ __forceinline__ float* seq_grad_row(const SeqGradArgs& G, int count) {
-    const size_t wave = threadIdx.x >> 6, len = (size_t)count * kSeqGradSums;
-    return G.lds_rows ? seq_grad_lds + wave * len : G.rows + ((size_t)blockIdx.x * (SS_BLOCK / 64) + wave) * len;
-}
-
-// LDS rows -> workspace: the 4 waves' rows added in wave order into the workgroup's one row
-__device__ __forceinline__ void seq_grad_flush(const SeqGradArgs& G, int count) {
-    if (!G.lds_rows) return;
-    __syncthreads();
-    const size_t len = (size_t)count * kSeqGradSums;
-    float* dst = G.rows + (size_t)blockIdx.x * len;
-    for (size_t j = threadIdx.x; j < len; j += SS_BLOCK) {
-        float acc = seq_grad_lds[j];
-#pragma unroll
-        for (int w = 1; w < SS_BLOCK / 64; ++w) acc += seq_grad_lds[w * len + j];
-        dst[j] = acc;
-    }
-}
-
-__device__ __forceinline__ void seq_vjp_rgb_body(const SunskyKArgs& K, const SeqArgs& A, const SeqGradArgs& G,
-                                                 const float* __restrict__ wx, const float* __restrict__ wy,
-                                                 const float* __restrict__ wz, const uint8_t* __restrict__ active,
-                                                 size_t n) {
-    const int count = A.count;
-    float* row = seq_grad_row(G, count);
-    const float cie = (float)kCieYNormalization;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    bool first = true;
-    // the loop bound is the workgroup's: every lane of a wave takes part in the wave sums
-    for (size_t b = (size_t)blockIdx.x * blockDim.x; b < n; b += stride) {
-        const size_t i = b + threadIdx.x;
-        bool m = false;
-        float3_ wo = mk3(0.f, 0.f, 1.f);
-        float cot[3] = {0.f, 0.f, 0.f};
-        if (i < n) {
-            m = !active || active[i] != 0;
-            wo = to_local(K, flip3<true>(wx[i], wy[i], wz[i]));
-#pragma unroll
-            for (int c = 0; c < 3; ++c) cot[c] = G.dout[(size_t)c * G.dstride + i] * cie;
-        }
-        const SeqDir s = seq_dir<false>(wo, m);
-        SeqGradHot cur = seq_grad_load(A.frames, G.grads, 3, 0);
-#pragma unroll 1
-        for (int k = 0; k < count; ++k) {
-            const SeqGradHot nxt = seq_grad_load(A.frames, G.grads, 3, k + 1 < count ? k + 1 : k);
-            const DirTerms t = seq_frame_terms<false>(s, cur.sn, K.cos_cutoff);
-            const float sg = sin_gamma(t);
-            const UnitAngleTan ua = unit_angle_tan_setup(cur.sn, s.wo);
-            float dgs[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) dgs[a] = unit_angle_tan_apply(ua, cur.dl[a]);
-            seq_cfloat_p rec = seq_record(A.frames, 3, k), grec = seq_grad_record(G.grads, 3, k);
-            float gw = 0.f, gt = 0.f, ge = 0.f, gm = 0.f;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const SeqSkySide S = seq_sky_side(seq_chan<false>(rec, 3, c), grec + c * 10,
-                                                  grec + seq_grad_block(3) + c * 10, t, sg);
-                const float cs = cot[c] * K.sky_scale;
-                gw = fmaf(cs, S.v, gw);
-                gt = fmaf(cs, S.t, gt);
-                ge = fmaf(cs, S.e, ge);
-                gm = fmaf(cs, S.gm, gm);
-            }
-            float g[kSeqGradSums] = {gw, gt, gm * dgs[0], gm * dgs[1], gm * dgs[2]};
-            if (t.hit_sun) seq_disc_vjp_rgb(K, A, k, t, sg, dgs, cot, g);
-            seq_grad_accumulate(g, ge, cur, t.active, row, k, first);
-            cur = nxt;
-        }
-        first = false;
-    }
-    seq_grad_flush(G, count);
-}
-
-// Spectral: frames outside, the wavelength list inside, so a frame's direction terms and its
-// wave sums are formed once for all planes.  An invalid wavelength adds nothing.
-__device__ __forceinline__ void seq_vjp_spec_body(const SunskyKArgs& K, const SeqArgs& A, const SeqGradArgs& G,
-                                                  const LambdaSet& L, const float* __restrict__ wx,
-                                                  const float* __restrict__ wy, const float* __restrict__ wz,
-                                                  const uint8_t* __restrict__ active, size_t n) {
-    const int count = A.count;
-    float* row = seq_grad_row(G, count);
-    constexpr int gb = seq_grad_block(kNbWavelengths);
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    bool first = true;
-    for (size_t b = (size_t)blockIdx.x * blockDim.x; b < n; b += stride) {
-        const size_t i = b + threadIdx.x;
-        const bool in = i < n;
-        bool m = false;
-        float3_ wo = mk3(0.f, 0.f, 1.f);
-        if (in) {
-            m = !active || active[i] != 0;
-            wo = to_local(K, flip3<true>(wx[i], wy[i], wz[i]));
-        }
-        const SeqDir s = seq_dir<false>(wo, m);
-        SeqGradHot cur = seq_grad_load(A.frames, G.grads, kNbWavelengths, 0);
-#pragma unroll 1
-        for (int k = 0; k < count; ++k) {
-            const SeqGradHot nxt = seq_grad_load(A.frames, G.grads, kNbWavelengths, k + 1 < count ? k + 1 : k);
-            const DirTerms t = seq_frame_terms<false>(s, cur.sn, K.cos_cutoff);
-            const float sg = sin_gamma(t);
-            const UnitAngleTan ua = unit_angle_tan_setup(cur.sn, s.wo);
-            float dgs[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) dgs[a] = unit_angle_tan_apply(ua, cur.dl[a]);
-            seq_cfloat_p rec = seq_record(A.frames, kNbWavelengths, k), grec = seq_grad_record(G.grads, kNbWavelengths, k);
-            float g[kSeqGradSums] = {0.f, 0.f, 0.f, 0.f, 0.f};
-            float ge = 0.f, gm = 0.f;
-#pragma unroll 1
-            for (int q = 0; q < L.m; ++q) {
-                const int lo = L.lo[q];
-                const float f = L.f[q];
-                if (f < 0.f) continue;
-                const float cot = in ? G.dout[(size_t)q * G.dstride + i] : 0.f;
-                const float wlo = f != 0.f ? 1.f - f : 1.f;   // lerp weights (f = 0: the low channel only)
-                const SeqSkySide S = seq_sky_side(seq_chan<false>(rec, kNbWavelengths, lo), grec + lo * 10,
-                                                  grec + gb + lo * 10, t, sg);
-                float v = wlo * S.v, dt = wlo * S.t, de = wlo * S.e, dm = wlo * S.gm;
-                if (f != 0.f) {   // f != 0 means lo <= 9: the high channel exists
-                    const SeqSkySide H = seq_sky_side(seq_chan<false>(rec, kNbWavelengths, lo + 1), grec + (lo + 1) * 10,
-                                                      grec + gb + (lo + 1) * 10, t, sg);
-                    v = fmaf(f, H.v, v);
-                    dt = fmaf(f, H.t, dt);
-                    de = fmaf(f, H.e, de);
-                    dm = fmaf(f, H.gm, dm);
-                }
-                const float cs = cot * K.sky_scale;
-                g[0] = fmaf(cs, v, g[0]);
-                g[1] = fmaf(cs, dt, g[1]);
-                ge = fmaf(cs, de, ge);
-                gm = fmaf(cs, dm, gm);
-                if (t.hit_sun) seq_disc_vjp_spec(K, A, k, t, sg, dgs, lo, f, cot, g);
-            }
-#pragma unroll
-            for (int a = 0; a < 3; ++a) g[2 + a] = fmaf(gm, dgs[a], g[2 + a]);
-            seq_grad_accumulate(g, ge, cur, t.active, row, k, first);
-            cur = nxt;
-        }
-        first = false;
-    }
-    seq_grad_flush(G, count);
-}
-
-// Both names of each kernel (the launch layer's table loads name_fast and name_ref from both
-// code objects) run the one reference-precision body: the gradient has no FAST form.
-#define SS_SEQUENCE_VJP(SUFFIX)                                                                                \
-    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_eval_vjp_rgb##SUFFIX(               \
-        const SunskyKArgs* __restrict__ Kp, SeqArgs A, SeqGradArgs G, const float* wx, const float* wy,        \
-        const float* wz, const uint8_t* active, size_t n) {                                                    \
-        seq_vjp_rgb_body(*Kp, A, G, wx, wy, wz, active, n);                                                    \
-    }                                                                                                          \
-    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_eval_vjp_spec##SUFFIX(              \
-        const SunskyKArgs* __restrict__ Kp, SeqArgs A, SeqGradArgs G, LambdaSet L, const float* wx,            \
-        const float* wy, const float* wz, const uint8_t* active, size_t n) {                                   \
-        seq_vjp_spec_body(*Kp, A, G, L, wx, wy, wz, active, n);                                                \
-    }
-SS_SEQUENCE_VJP(_fast)
-SS_SEQUENCE_VJP(_ref)
-
-// One wave per frame: lane l adds rows l, l + 64, ... in row order, the wave adds the lanes'
-// sums (wave_sum), lane 0 accumulates into the outputs that are not NULL.
-extern "C" __global__ __launch_bounds__(kSeqGradReduceBlock) void sunsky_sequence_grad_reduce(
-    const float* __restrict__ rows, unsigned nrows, int count, float* grad_weight, float* grad_turbidity,
-    float* grad_sun_dir) {
-    for (int k = blockIdx.x; k < count; k += gridDim.x) {
-        float acc[kSeqGradSums] = {0.f, 0.f, 0.f, 0.f, 0.f};
-        for (unsigned r = threadIdx.x; r < nrows; r += kSeqGradReduceBlock) {
-            const float* p = rows + ((size_t)r * count + k) * kSeqGradSums;
-#pragma unroll
-            for (int c = 0; c < kSeqGradSums; ++c) acc[c] += p[c];
-        }
-#pragma unroll
-        for (int c = 0; c < kSeqGradSums; ++c) acc[c] = wave_sum(acc[c]);
-        if (threadIdx.x == 0) {
-            if (grad_weight) grad_weight[k] += acc[0];
-            if (grad_turbidity) grad_turbidity[k] += acc[1];
-            if (grad_sun_dir)
-                for (int a = 0; a < 3; ++a) grad_sun_dir[3 * k + a] += acc[2 + a];
-        }
-    }
-}
-
-// ======================================================================
-// Sequence sampling (sunsky_sequence_sample_direction / _pdf_direction; the distribution is
-// SeqSampling's, sunsky_kernel_args.h).  A sample is a sky pick (u1 < w_sky: a row of the table
-// from the marginal with u2, a column from the row's distribution with the reused u1, uniform
-// within the cell) or a sun pick (a frame from the q distribution with the reused u1, then
-// square_to_uniform_cone about that frame's sun, sunsky.cpp:697-701).  Its pdf and the pdf of a
-// given direction are ONE function of the local direction: the cell's table value plus
-// sum_k q_k [dot(s_k, wo) >= cos_cutoff], the cone test seq_frame_terms makes (hit_sun).  The
-// sampler evaluates the weight's numerator with the accumulate loop, so that sum rides along as
-// one more accumulator, q_k beside the header's scalar load; the pdf kernel walks 16-byte
-// {s_k, q_k} records instead, one address per wave.  Both add in frame order: a sample's
-// ds.pdf is bit for bit pdf_direction(ds.d).
-// ======================================================================
-
-// First entry of an inclusive normalised CDF above u (entries past the last non-zero one hold
-// 1, so u < 1 never reaches them), by bisection: index in [0, n - 1] for every u, NaN included
-__device__ __forceinline__ int seq_cdf_search(const float* __restrict__ cdf, int n, float u) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (cdf[mid] <= u) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// sample_reuse: the entry and the position of u within it, in [0, 1)
-__device__ __forceinline__ int seq_cdf_sample(const float* __restrict__ cdf, int n, float u, float* reused) {
-    const int j = seq_cdf_search(cdf, n, u);
-    const float lo = j > 0 ? cdf[j - 1] : 0.f, hi = cdf[j];
-    const float t = hi > lo ? (u - lo) / (hi - lo) : 0.f;
-    *reused = fminf(fmaxf(t, 0.f), kOneMinusEpsilon);
-    return j;
-}
-
-// The table value of the cell that holds local direction wo (any wo: the indices are clamped)
-__device__ __forceinline__ float seq_sky_cell(const SeqSampling& S, float3_ wo) {
-    const int row = (int)fminf(fmaxf(wo.z * (float)S.nz, 0.f), (float)(S.nz - 1));
-    float phi = atan2_fast(wo.y, wo.x);
-    phi = phi < 0.f ? phi + kTwoPi : phi;
-    const int col = (int)fminf(fmaxf(phi * S.inv_dphi, 0.f), (float)(S.nphi - 1));
-    return S.f[(size_t)row * (size_t)S.nphi + (size_t)col];
-}
-
-__device__ __forceinline__ float seq_pdf_combine(const SeqSampling& S, float fcell, float qsum, bool active) {
-    return active ? fmaf(S.sky_coef, fcell, S.sun_coef * qsum) : 0.f;
-}
-
-// sum_k q_k [dot(s_k, wo) >= cos_cutoff] over the compact records, in frame order
-__device__ __forceinline__ float seq_cone_sum(const float* suns, int count, float3_ wo, float cos_cutoff) {
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wold-style-cast"
-    seq_cfloat_p p = (seq_cfloat_p)suns;
-#pragma clang diagnostic pop
-    float qsum = 0.f;
-#pragma unroll 4
-    for (int k = 0; k < count; ++k) {
-        const float d = dot3(mk3(p[4 * k], p[4 * k + 1], p[4 * k + 2]), wo);
-        qsum += d >= cos_cutoff ? p[4 * k + 3] : 0.f;
-    }
-    return qsum;
-}
-
-// The sample map, in the local frame
-template <bool FAST>
-__device__ __forceinline__ float3_ seq_sample_local(const SunskyKArgs& K, const SeqSampling& S, int count, float u1,
-                                                    float u2) {
-    if (u1 < S.w_sky) {
-        const float a = fminf(u1 / S.w_sky, kOneMinusEpsilon);
-        float t1, t2;
-        const int i = seq_cdf_sample(S.row_cdf, S.nz, u2, &t2);
-        const int j = seq_cdf_sample(S.cell_cdf + (size_t)i * (size_t)S.nphi, S.nphi, a, &t1);
-        const float z = fminf(((float)i + t2) / (float)S.nz, 1.f);
-        const float phi = ((float)j + t1) * S.dphi;
-        float sp, cp;
-        sincos_sel<FAST>(phi, &sp, &cp);
-        const float st = safe_sqrt_sel<FAST>(fmaf(-z, z, 1.f));
-        return mk3(st * cp, st * sp, z);
-    }
-    const float a = fminf((u1 - S.w_sky) / (1.f - S.w_sky), kOneMinusEpsilon);
-    float t1;
-    const int k = seq_cdf_sample(S.frame_cdf, count, a, &t1);
-    const float* r = S.suns + 4 * (size_t)k;
-    const float3_ sn = mk3(r[0], r[1], r[2]);
-    float3_ fs, ft;
-    coordinate_system(sn, &fs, &ft);   // Frame3f(local sun), as the emitter's sun_s / sun_t
-    float3_ sd = frame_to_world(fs, ft, sn, uniform_cone_dev<FAST>(t1, u2, K.cos_cutoff));
-    // cos theta <= 1, as the sky pick's min(): next to the zenith a unit fp32 vector can round to
-    // z = 1 + 6e-8, where the disc term's elevation pi/2 - acos(z) is NaN (measured with a sun at
-    // 89.9 degrees: a handful of weights per 2^16 zeroed as not finite)
-    sd.z = fminf(sd.z, 1.f);
-    return sd;
-}
-
-// What both samplers do before and beside the frame loop: the sample, ds.d / ds.dist / ds.p
-template <bool FAST>
-__device__ __forceinline__ SeqDir seq_sample_dir(const SunskyKArgs& K, const SeqSampling& S, int count,
-                                                 const SeqSampleIO& io, size_t i) {
-    bool act = !io.active || io.active[i] != 0;
-    const float3_ sd = seq_sample_local<FAST>(K, S, count, io.ux[i], io.uy[i]);
-    act = act && (sd.z >= 0.f);
-    const float3_ d = to_world(K, sd);
-    store_nt(d.x, io.dx + i);
-    store_nt(d.y, io.dy + i);
-    store_nt(d.z, io.dz + i);
-    if (io.dist || io.opx) {
-        const float3_ itp = io.px ? mk3(io.px[i], io.py[i], io.pz[i]) : mk3(0.f, 0.f, 0.f);
-        const float3_ rel = mk3(itp.x - K.bs_center[0], itp.y - K.bs_center[1], itp.z - K.bs_center[2]);
-        const float dd = 2.f * fmaxf(K.bs_radius, sqrtf(dot3(rel, rel)));
-        if (io.dist) store_nt(dd, io.dist + i);
-        if (io.opx) {
-            store_nt(fmaf(d.x, dd, itp.x), io.opx + i);
-            store_nt(fmaf(d.y, dd, itp.y), io.opy + i);
-            store_nt(fmaf(d.z, dd, itp.z), io.opz + i);
-        }
-    }
-    // the weight is eval(si{wi = -d}) / pdf at the direction the caller gets: d back in the local frame
-    return seq_dir<FAST>(to_local(K, d), act);
-}
-
-template <bool FAST>
-__device__ __forceinline__ float seq_weight(float e, float pd, float inv_pd, bool active) {
-    const float w = FAST ? e * inv_pd : e / pd;
-    return active && isfinite(w) ? w : 0.f;
-}
-
-template <bool FAST>
-__device__ __forceinline__ void seq_sample_rgb_body(const SunskyKArgs& K, const SeqArgs& A, const SeqSampling& S,
-                                                    const SeqSampleIO& io, size_t n) {
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    const int chans[3] = {0, 1, 2};
-    const int count = A.count;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const SeqDir s = seq_sample_dir<FAST>(K, S, count, io, i);
-        const float fcell = seq_sky_cell(S, s.wo);
-        float acc[3] = {0.f, 0.f, 0.f}, qsum = 0.f;
-        // seq_rgb_body's frame loop with the cone sum as a fourth accumulator
-        SeqHot<FAST, 3> cur = seq_load<FAST, 3>(A.frames, 3, 0, chans);
-        float q = seq_record(A.frames, 3, 0)[kSeqFrameQ];
-#pragma unroll 1
-        for (int k = 0; k < count; ++k) {
-            const int kn = k + 1 < count ? k + 1 : k;
-            const SeqHot<FAST, 3> nxt = seq_load<FAST, 3>(A.frames, 3, kn, chans);
-            const float qn = seq_record(A.frames, 3, kn)[kSeqFrameQ];
-            const DirTerms t = seq_frame_terms<FAST>(s, cur.sn, K.cos_cutoff);
-            float v[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) v[c] = sky_eval<FAST>(cur.ch[c], t, K.sky_scale);
-            if (t.hit_sun) seq_disc_rgb<FAST>(K, A, k, t, v);
-            if constexpr (!FAST) {
-                const float cie = (float)kCieYNormalization;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) v[c] = v[c] * cie;
-            }
-#pragma unroll
-            for (int c = 0; c < 3; ++c) acc[c] = fmaf(cur.w, v[c], acc[c]);
-            qsum += t.hit_sun ? q : 0.f;
-            cur = nxt;
-            q = qn;
-        }
-        const float pd = seq_pdf_combine(S, fcell, qsum, s.active);
-        store_nt(pd, io.pdf + i);
-        const float inv_pd = fdiv<FAST>(1.f, pd);
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-            store_nt(seq_weight<FAST>(acc[c], pd, inv_pd, s.active), io.weight + (size_t)c * io.wstride + i);
-    }
-}
-
-// Spectral: the cone sum rides in the first wavelength's frame loop; a list with no valid
-// wavelength takes it from the compact records (the same sum)
-template <bool FAST>
-__device__ __forceinline__ void seq_sample_spec_body(const SunskyKArgs& K, const SeqArgs& A, const SeqSampling& S,
-                                                     const LambdaSet& L, const SeqSampleIO& io, size_t n) {
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    const int count = A.count;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const SeqDir s = seq_sample_dir<FAST>(K, S, count, io, i);
-        const float fcell = seq_sky_cell(S, s.wo);
-        bool have_pd = false;
-        float pd = 0.f, inv_pd = 0.f;
-#pragma unroll 1
-        for (int qi = 0; qi < L.m; ++qi) {
-            const int lo = L.lo[qi];
-            const float f = L.f[qi];
-            float acc = 0.f;
-            if (f >= 0.f) {
-                float qsum = 0.f;
-                const int chans[2] = {lo, lo + 1 < kNbWavelengths ? lo + 1 : lo};
-                SeqHot<FAST, 2> cur = seq_load<FAST, 2>(A.frames, kNbWavelengths, 0, chans);
-                float q = seq_record(A.frames, kNbWavelengths, 0)[kSeqFrameQ];
-#pragma unroll 1
-                for (int k = 0; k < count; ++k) {
-                    const int kn = k + 1 < count ? k + 1 : k;
-                    const SeqHot<FAST, 2> nxt = seq_load<FAST, 2>(A.frames, kNbWavelengths, kn, chans);
-                    const float qn = seq_record(A.frames, kNbWavelengths, kn)[kSeqFrameQ];
-                    const DirTerms t = seq_frame_terms<FAST>(s, cur.sn, K.cos_cutoff);
-                    float v = sky_eval<FAST>(cur.ch[0], t, K.sky_scale);
-                    if (f != 0.f) v = lerpf_(v, sky_eval<FAST>(cur.ch[1], t, K.sky_scale), f);
-                    if (t.hit_sun) v = seq_disc_spec<FAST>(K, A, k, t, lo, f, v);
-                    acc = fmaf(cur.w, v, acc);
-                    qsum += t.hit_sun ? q : 0.f;
-                    cur = nxt;
-                    q = qn;
-                }
-                if (!have_pd) {
-                    pd = seq_pdf_combine(S, fcell, qsum, s.active);
-                    inv_pd = fdiv<FAST>(1.f, pd);
-                    have_pd = true;
-                }
-            }
-            store_nt(f >= 0.f ? seq_weight<FAST>(acc, pd, inv_pd, s.active) : 0.f, io.weight + (size_t)qi * io.wstride + i);
-        }
-        if (!have_pd) pd = seq_pdf_combine(S, fcell, seq_cone_sum(S.suns, count, s.wo, K.cos_cutoff), s.active);
-        store_nt(pd, io.pdf + i);
-    }
-}
-
-// pdf_direction: the cell's value and the cone sum; the same in both precisions
-__device__ __forceinline__ void seq_pdf_body(const SunskyKArgs& K, const SeqSampling& S, int count, const float* dx,
-                                             const float* dy, const float* dz, const uint8_t* active, size_t n,
-                                             float* __restrict__ pdf) {
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const bool m = !active || active[i] != 0;
-        const float3_ wo = to_local(K, mk3(dx[i], dy[i], dz[i]));
-        const float fcell = seq_sky_cell(S, wo);
-        const float qsum = seq_cone_sum(S.suns, count, wo, K.cos_cutoff);
-        store_nt(seq_pdf_combine(S, fcell, qsum, m && (wo.z >= 0.f)), pdf + i);
-    }
-}
-
-#define SS_SEQUENCE_SAMPLING(SUFFIX, FAST)                                                                     \
-    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_sample_rgb##SUFFIX(                 \
-        const SunskyKArgs* __restrict__ Kp, SeqArgs A, SeqSampling S, SeqSampleIO io, size_t n) {              \
-        seq_sample_rgb_body<FAST>(*Kp, A, S, io, n);                                                           \
-    }                                                                                                          \
-    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_sample_spec##SUFFIX(                \
-        const SunskyKArgs* __restrict__ Kp, SeqArgs A, SeqSampling S, LambdaSet L, SeqSampleIO io, size_t n) { \
-        seq_sample_spec_body<FAST>(*Kp, A, S, L, io, n);                                                       \
-    }                                                                                                          \
-    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_pdf##SUFFIX(                        \
-        const SunskyKArgs* __restrict__ Kp, SeqSampling S, int count, const float* dx, const float* dy,        \
-        const float* dz, const uint8_t* active, size_t n, float* pdf) {                                        \
-        seq_pdf_body(*Kp, S, count, dx, dy, dz, active, n, pdf);                                               \
-    }
-SS_SEQUENCE_SAMPLING(_fast, true)
-SS_SEQUENCE_SAMPLING(_ref, false)
-
-// prepare_sampling's table: cell (i, j) = Y(sum_k w_k sky_k(centre)), the accumulate loop in
-// reference precision with the disc branch off, one cell per lane.  Y: the RGB luminance
-// weights, or sum_c cie_y[c] L_c / 11 over the 11 nodes (quad_finish's).
-// The frame loop of the sky tables (sunsky_sequence_table, sunsky_sequence_irradiance_table):
-// sum_k w_k sky_k(s) of the N channels c[], reference precision, the disc branch off, added in
-// frame order as fma(w_k, v, acc).  RGB = true: N = 3 planes, each x MI_CIE_Y_NORMALIZATION.
-// Otherwise one plane: channel c[0], or (N = 2) the lerp of c[0] and c[1] by f != 0, as
-// seq_spec_body forms a wavelength between two nodes.
-// One frame's term sky_k(s), unweighted, of the record `cur`: what seq_sky_sum weighs and adds,
-// and what sunsky_sequence_irradiance_grad_fold contracts with the adjoint image.
-template <bool RGB, int N>
-__device__ __forceinline__ void seq_sky_frame(const SunskyKArgs& K, const SeqHot<false, N>& cur, const SeqDir& s, float f,
-                                              float (&v)[RGB ? 3 : 1]) {
-    static_assert(RGB ? N == 3 : (N == 1 || N == 2), "3 RGB planes, or one plane from one or two nodes");
-    const DirTerms t = seq_frame_terms<false>(s, cur.sn, K.cos_cutoff);
-    if constexpr (RGB) {
-        const float cie = (float)kCieYNormalization;
-#pragma unroll
-        for (int p = 0; p < 3; ++p) v[p] = sky_eval<false>(cur.ch[p], t, K.sky_scale) * cie;
-    } else {
-        v[0] = sky_eval<false>(cur.ch[0], t, K.sky_scale);
-        if constexpr (N == 2)
-            if (f != 0.f) v[0] = lerpf_(v[0], sky_eval<false>(cur.ch[1], t, K.sky_scale), f);
-    }
-}
-
-template <bool RGB, int N>
-__device__ __forceinline__ void seq_sky_sum(const SunskyKArgs& K, const SeqArgs& A, const SeqDir& s, const int (&c)[N],
-                                            float f, float (&acc)[RGB ? 3 : 1]) {
-    const int nch = RGB ? 3 : kNbWavelengths, count = A.count;
-#pragma unroll
-    for (int p = 0; p < (RGB ? 3 : 1); ++p) acc[p] = 0.f;
-    SeqHot<false, N> cur = seq_load<false, N>(A.frames, nch, 0, c);
-#pragma unroll 1
-    for (int k = 0; k < count; ++k) {
-        const SeqHot<false, N> nxt = seq_load<false, N>(A.frames, nch, k + 1 < count ? k + 1 : k, c);
-        float v[RGB ? 3 : 1];
-        seq_sky_frame<RGB, N>(K, cur, s, f, v);
-#pragma unroll
-        for (int p = 0; p < (RGB ? 3 : 1); ++p) acc[p] = fmaf(cur.w, v[p], acc[p]);
-        cur = nxt;
-    }
-}
-
-extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_table(const SunskyKArgs* __restrict__ Kp,
-                                                                             SeqArgs A, SeqTableArgs T) {
-    const SunskyKArgs& K = *Kp;
-    const size_t n = (size_t)T.nz * (size_t)T.nphi, stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const float3_ wo = seq_cell_centre(T.nz, T.nphi, (int)(i / (size_t)T.nphi), (int)(i % (size_t)T.nphi));
-        const SeqDir s = seq_dir<false>(wo, true);
-        float y = 0.f;
-        if (K.variant == kRGB) {
-            const int chans[3] = {0, 1, 2};
-            float acc[3];
-            seq_sky_sum<true, 3>(K, A, s, chans, 0.f, acc);
-            y = luminance_rgb(acc);
-        } else {
-#pragma unroll 1
-            for (int c = 0; c < kNbWavelengths; ++c) {
-                const int chans[1] = {c};
-                float acc[1];
-                seq_sky_sum<false, 1>(K, A, s, chans, 0.f, acc);
-                y = fmaf(T.cie_y[c], acc[0], y);
-            }
-            y = y / (float)kNbWavelengths;
-        }
-        T.f[i] = fmaxf(y, 0.f);
-    }
-}
-
-// prepare_sampling's suns: B_k = Y of frame k's disc term alone at the disc centre (what
-// seq_disc_* add at wo = s_k), reference precision.  One wave per frame: the disc branch reads
-// its record with one address per wave.
-extern "C" __global__ __launch_bounds__(64) void sunsky_sequence_suns(const SunskyKArgs* __restrict__ Kp, SeqArgs A,
-                                                                      SeqTableArgs T) {
-    const SunskyKArgs& K = *Kp;
-    for (int k = blockIdx.x; k < A.count; k += gridDim.x) {
-        seq_cfloat_p rec = seq_record(A.frames, K.nch, k);
-        const float3_ sn = mk3(rec[0], rec[1], rec[2]);
-        const DirTerms t = seq_frame_terms<false>(seq_dir<false>(sn, true), sn, K.cos_cutoff);
-        float y = 0.f;
-        if (t.hit_sun) {
-            if (K.variant == kRGB) {
-                float v[3] = {0.f, 0.f, 0.f};
-                seq_disc_rgb<false>(K, A, k, t, v);
-                y = luminance_rgb(v) * (float)kCieYNormalization;
-            } else {
-#pragma unroll 1
-                for (int c = 0; c < kNbWavelengths; ++c) y = fmaf(T.cie_y[c], seq_disc_spec<false>(K, A, k, t, c, 0.f, 0.f), y);
-                y = y / (float)kNbWavelengths;
-            }
-        }
-        if (threadIdx.x == 0) T.B[k] = fmaxf(y, 0.f);
-    }
-}
-
-// ======================================================================
-// Irradiance on oriented receivers (sunsky_sequence_prepare_irradiance / _irradiance; the
-// definition is in sunsky_amd.h):
-//   E_p(n) = sum_i sum_j omega R_p[i, j] max(0, n_l . c_ij) + sum_k w_k F_k[p] max(0, n_l . s_k)
-// prepare_irradiance runs the two table kernels below and stages one image of 16-byte aligned
-// records (direction, then the weighted plane values: seq_irr_record); the hot path is a
-// receiver x record contraction with one receiver per lane.
-// ======================================================================
-
-// R_p[i, j] = (sum_k w_k sky_k(c_ij))_p: sunsky_sequence_table's frame loop with the planes
-// kept.  One cell per lane; spectral: one pass per requested wavelength (an invalid one: 0).
-extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_irradiance_table(
-    const SunskyKArgs* __restrict__ Kp, SeqArgs A, SeqIrrTableArgs T) {
-    const SunskyKArgs& K = *Kp;
-    const size_t n = (size_t)T.nz * (size_t)T.nphi, stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const float3_ wo = seq_cell_centre(T.nz, T.nphi, (int)(i / (size_t)T.nphi), (int)(i % (size_t)T.nphi));
-        const SeqDir s = seq_dir<false>(wo, true);
-        if (K.variant == kRGB) {
-            const int chans[3] = {0, 1, 2};
-            float acc[3];
-            seq_sky_sum<true, 3>(K, A, s, chans, 0.f, acc);
-#pragma unroll
-            for (int p = 0; p < 3; ++p) T.sky[(size_t)p * n + i] = acc[p];
-        } else {
-#pragma unroll 1
-            for (int q = 0; q < T.planes; ++q) {
-                const int lo = T.L.lo[q];
-                const float f = T.L.f[q];
-                float acc[1] = {0.f};
-                if (f >= 0.f) {
-                    const int chans[2] = {lo, lo + 1 < kNbWavelengths ? lo + 1 : lo};
-                    seq_sky_sum<false, 2>(K, A, s, chans, f, acc);
-                }
-                T.sky[(size_t)q * n + i] = acc[0];
-            }
-        }
-    }
-}
-
-// F_k[p]: frame k's disc term alone integrated over its cone by the 4 x 16 rule
-// (seq_flux_point), reference precision.  One wave per frame, lane = point (a, b): the
-// direction through Frame(s_k), its cos theta and elevation segment as eval takes them, cos psi
-// = u_a as given (not recomputed from the rounded direction, no cone test); 0 below the horizon
-// and for a sun below it.  The 64 weighted values are added by wave_sum's fixed tree.
-extern "C" __global__ __launch_bounds__(64) void sunsky_sequence_irradiance_flux(const SunskyKArgs* __restrict__ Kp,
-                                                                                 SeqArgs A, SeqIrrTableArgs T) {
-    const SunskyKArgs& K = *Kp;
-    const int lane = threadIdx.x;
-    const SeqFluxPoint pt = seq_flux_point(T.sin2_half_ap, lane / kSeqFluxNphi, lane % kSeqFluxNphi);
-    const float ring = kTwoPi / (float)kSeqFluxNphi;
-    for (int k = blockIdx.x; k < A.count; k += gridDim.x) {
-        seq_cfloat_p rec = seq_record(A.frames, K.nch, k);
-        const float3_ sn = mk3(rec[0], rec[1], rec[2]);
-        const RadianceStage rs = seq_sun_stage(rec);
-        float3_ fs, ft;
-        coordinate_system(sn, &fs, &ft);
-        const float3_ d = frame_to_world(fs, ft, sn, mk3(pt.x, pt.y, pt.z));
-        const bool up = sn.z >= 0.f && d.z >= 0.f;
-        float xs = 0.f;
-        const int pos = up ? seq_segment_ref(K, fminf(d.z, 1.f), &xs) : 0;
-        if (K.variant == kRGB) {
-            float v[3] = {0.f, 0.f, 0.f};
-            if (up) seq_disc_rgb_at(K, A.sun_rad_ds, A.sun_block, rs, pos, xs, pt.u, v);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float sum = wave_sum(pt.W * (v[c] * (float)kCieYNormalization));
-                if (lane == 0) T.flux[(size_t)c * A.count + k] = ring * sum;
-            }
-        } else {
-#pragma unroll 1
-            for (int q = 0; q < T.planes; ++q) {
-                const int lo = T.L.lo[q];
-                const float f = T.L.f[q];
-                float v = 0.f;
-                if (up && f >= 0.f) v = seq_disc_spec_at(K, A.sun_rad_ds, A.sun_block, rs, pos, xs, pt.u, lo, f, 0.f);
-                const float sum = wave_sum(pt.W * v);
-                if (lane == 0) T.flux[(size_t)q * A.count + k] = ring * sum;
-            }
-        }
-    }
-}
-
-// Two receivers per lane: every operation of the contraction is one packed fp32 instruction
-// over the pair (the record's scalar broadcast to both halves), except the clamp.
-typedef float seq_f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ seq_f2 seq_fma2(seq_f2 a, float b, seq_f2 c) {
-    const seq_f2 bb = {b, b};
-    return __builtin_elementwise_fma(a, bb, c);
-}
-
-// One pass of the contraction for the NP planes [p0, p0 + NP) of a lane's two receivers with
-// local normals (nx, ny, nz)[0 / 1].  The records are read through the constant address space
-// with one address per wave (scalar loads into SGPRs, REC floats apart; REC = 0: `rec` at run
-// time), so a lane's work per record and receiver is the dot product, the clamp and NP FMAs.
-// The order is the contract: a row's cells in column order into a row sum that starts at 0,
-// the row sums in row order into the plane's sum, then the suns in list order, every
-// product-and-add one fma; the two receivers of a lane never meet.
-//
-// HZ (sunsky_sequence_irradiance_horizon): the column loop is cut into the profile's
-// sectors (their length is wave-uniform).  Per row and sector the lane's two h values, loaded one
-// sector ahead of their use, give v = clamp(fma(-h, n_z, i + 1), 0, 1) once; per cell one packed
-// multiply (the clamped cosine times v) sits beside the forward's instructions.  A sun counts
-// when s_k.z >= h of its column's sector.  h: elements e0 and e1 of the sector's plane in global
-// memory (coalesced over receivers; one address for a shared profile), read again in every row
-// and served by the caches (a copy per lane in LDS was measured and lost: DESIGN.md).
-// The cell loop is unrolled by 4 records; passes of more than 8 planes (the per-frame series')
-// by SS_SEQ_IRR_WIDE_UNROLL = 2: four 112-byte records want more scalar registers than there are
-// (measured against 4 and 1: profiles/HISTORY.md).
-#ifndef SS_SEQ_IRR_WIDE_UNROLL
-#define SS_SEQ_IRR_WIDE_UNROLL 2
-#endif
-template <int NP, int REC, bool HZ = false>
-__device__ __forceinline__ void seq_irr_pass(const SeqIrradiance& S, int rec, int p0, seq_f2 nx, seq_f2 ny, seq_f2 nz,
-                                             seq_f2 (&acc)[NP], const SeqIrrHorizon* Z = nullptr, size_t e0 = 0,
-                                             size_t e1 = 0) {
-    if constexpr (REC != 0) rec = REC;
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wold-style-cast"
-    seq_cfloat_p r = (seq_cfloat_p)__builtin_assume_aligned(S.cells, 16) + 3 + p0;
-    seq_cfloat_p u = (seq_cfloat_p)__builtin_assume_aligned(S.suns, 16) + 3 + p0;
-#pragma clang diagnostic pop
-    const seq_f2 zero = {0.f, 0.f};
-    // max(0, n . d) for both receivers, d the direction in front of the plane values at q
-    auto cosine = [&](seq_cfloat_p q) {
-        const seq_f2 d = seq_fma2(nz, q[-1 - p0], seq_fma2(ny, q[-2 - p0], nx * q[-3 - p0]));
-        return __builtin_elementwise_max(d, zero);
-    };
-#pragma unroll
-    for (int p = 0; p < NP; ++p) acc[p] = zero;
-    if constexpr (HZ) {
-        const seq_f2 one = {1.f, 1.f}, fnz = {(float)S.nz, (float)S.nz};
-        const int sectors = Z->sectors, len = Z->sector_len;
-        // the lane's two h values of sector b
-        auto profile = [&](int b) {
-            const float* q = Z->h + (size_t)b * Z->stride;
-            const seq_f2 h = {q[e0], q[e1]};
-            return h;
-        };
-#pragma unroll 1
-        for (int i = 0; i < S.nz; ++i) {
-            seq_f2 row[NP];
-#pragma unroll
-            for (int p = 0; p < NP; ++p) row[p] = zero;
-            const seq_f2 top = {(float)(i + 1), (float)(i + 1)};
-            seq_f2 h = profile(0);
-#pragma unroll 1
-            for (int b = 0; b < sectors; ++b) {
-                const seq_f2 next = profile(b + 1 < sectors ? b + 1 : 0);
-                const seq_f2 v = __builtin_elementwise_min(
-                    __builtin_elementwise_max(__builtin_elementwise_fma(-h, fnz, top), zero), one);
-#pragma unroll NP > 8 ? SS_SEQ_IRR_WIDE_UNROLL : 4
-                for (int j = 0; j < len; ++j, r += rec) {
-                    const seq_f2 c = cosine(r) * v;
-#pragma unroll
-                    for (int p = 0; p < NP; ++p) row[p] = seq_fma2(c, r[p], row[p]);
-                }
-                h = next;
-            }
-#pragma unroll
-            for (int p = 0; p < NP; ++p) acc[p] += row[p];
-        }
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wold-style-cast"
-        seq_cint_p cols = (seq_cint_p)Z->sun_cols;
-#pragma clang diagnostic pop
-#pragma unroll 1
-        for (int k = 0; k < S.nsuns; ++k, u += rec) {
-            const seq_f2 h = profile(cols[k] / len);
-            const float sz = u[-1 - p0];
-            seq_f2 c = cosine(u);
-            c[0] = sz >= h[0] ? c[0] : 0.f;
-            c[1] = sz >= h[1] ? c[1] : 0.f;
-#pragma unroll
-            for (int p = 0; p < NP; ++p) acc[p] = seq_fma2(c, u[p], acc[p]);
-        }
-        return;
-    }
-#pragma unroll 1
-    for (int i = 0; i < S.nz; ++i) {
-        seq_f2 row[NP];
-#pragma unroll
-        for (int p = 0; p < NP; ++p) row[p] = zero;
-#pragma unroll NP > 8 ? SS_SEQ_IRR_WIDE_UNROLL : 4
-        for (int j = 0; j < S.nphi; ++j, r += rec) {
-            const seq_f2 c = cosine(r);
-#pragma unroll
-            for (int p = 0; p < NP; ++p) row[p] = seq_fma2(c, r[p], row[p]);
-        }
-#pragma unroll
-        for (int p = 0; p < NP; ++p) acc[p] += row[p];
-    }
-#pragma unroll 1
-    for (int k = 0; k < S.nsuns; ++k, u += rec) {
-        const seq_f2 c = cosine(u);
-#pragma unroll
-        for (int p = 0; p < NP; ++p) acc[p] = seq_fma2(c, u[p], acc[p]);
-    }
-}
-
-// Two receivers per lane, t and t + ceil(n / 2) (both streams coalesced), grid-stride over the
-// pairs.  RGB: one pass of 3 planes over 32-byte records.  Spectral: passes of 8, 4, 2 and 1
-// planes (a plane's sum does not depend on the pass it is in).
-// HZ: under the horizon profiles Z; a lane's elements of a sector's plane are its receivers'
-// indices (the first one's for a missing second receiver), or 0 for a shared profile.
-template <bool RGB, bool HZ = false>
-__device__ __forceinline__ void seq_irradiance_body(const SunskyKArgs& K, const SeqIrradiance& S, const float* nx,
-                                                    const float* ny, const float* nz, const uint8_t* active, size_t n,
-                                                    float* __restrict__ out, size_t ostride,
-                                                    const SeqIrrHorizon* Z = nullptr) {
-    const size_t stride = (size_t)gridDim.x * blockDim.x, pairs = (n + 1) / 2;
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < pairs; t += stride) {
-        const size_t idx[2] = {t, t + pairs};
-        const bool has[2] = {true, idx[1] < n};
-        bool m[2];
-        float3_ nl[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const size_t i = has[h] ? idx[h] : t;
-            m[h] = !active || active[i] != 0;
-            nl[h] = to_local(K, mk3(nx[i], ny[i], nz[i]));
-        }
-        const seq_f2 lx = {nl[0].x, nl[1].x}, ly = {nl[0].y, nl[1].y}, lz = {nl[0].z, nl[1].z};
-        auto store = [&](int p, seq_f2 v) {
-            store_nt(m[0] ? v[0] : 0.f, out + (size_t)p * ostride + idx[0]);
-            if (has[1]) store_nt(m[1] ? v[1] : 0.f, out + (size_t)p * ostride + idx[1]);
-        };
-        size_t e0 = 0, e1 = 0;
-        if constexpr (HZ) {
-            e0 = Z->per_receiver ? idx[0] : 0;
-            e1 = Z->per_receiver ? (has[1] ? idx[1] : idx[0]) : 0;
-        }
-        if constexpr (RGB) {
-            seq_f2 acc[3];
-            seq_irr_pass<3, seq_irr_record(3), HZ>(S, 0, 0, lx, ly, lz, acc, Z, e0, e1);
-#pragma unroll
-            for (int p = 0; p < 3; ++p) store(p, acc[p]);
-        } else {
-            const int rec = seq_irr_record(S.planes);
-            int p0 = 0;
-            auto pass = [&](auto np) {
-                constexpr int NP = decltype(np)::value;
-                seq_f2 acc[NP];
-                seq_irr_pass<NP, 0, HZ>(S, rec, p0, lx, ly, lz, acc, Z, e0, e1);
-#pragma unroll
-                for (int p = 0; p < NP; ++p) store(p0 + p, acc[p]);
-                p0 += NP;
-            };
-#pragma unroll 1
-            while (S.planes - p0 >= 8) pass(std::integral_constant<int, 8>());
-            if (S.planes - p0 >= 4) pass(std::integral_constant<int, 4>());
-            if (S.planes - p0 >= 2) pass(std::integral_constant<int, 2>());
-            if (S.planes - p0 >= 1) pass(std::integral_constant<int, 1>());
-        }
-    }
-}
-
-// Both precisions' names run the same body: the tables are reference precision by definition
-#define SS_SEQUENCE_IRRADIANCE(SUFFIX)                                                                         \
-    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_irradiance_rgb##SUFFIX(             \
-        const SunskyKArgs* __restrict__ Kp, SeqIrradiance S, const float* nx, const float* ny, const float* nz, \
-        const uint8_t* active, size_t n, float* out, size_t ostride) {                                         \
-        seq_irradiance_body<true>(*Kp, S, nx, ny, nz, active, n, out, ostride);                                \
-    }                                                                                                          \
-    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_irradiance_spec##SUFFIX(            \
-        const SunskyKArgs* __restrict__ Kp, SeqIrradiance S, const float* nx, const float* ny, const float* nz, \
-        const uint8_t* active, size_t n, float* out, size_t ostride) {                                         \
-        seq_irradiance_body<false>(*Kp, S, nx, ny, nz, active, n, out, ostride);                               \
-    }
-SS_SEQUENCE_IRRADIANCE(_fast)
-SS_SEQUENCE_IRRADIANCE(_ref)
-
-// The same under a per-receiver (or one shared) horizon profile: sunsky_sequence_irradiance_horizon
-#define SS_SEQUENCE_IRRADIANCE_HORIZON(SUFFIX)                                                                 \
-    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_irradiance_horizon_rgb##SUFFIX(     \
-        const SunskyKArgs* __restrict__ Kp, SeqIrradiance S, SeqIrrHorizon Z, const float* nx, const float* ny, \
-        const float* nz, const uint8_t* active, size_t n, float* out, size_t ostride) {                        \
-        seq_irradiance_body<true, true>(*Kp, S, nx, ny, nz, active, n, out, ostride, &Z);                      \
-    }                                                                                                          \
-    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_irradiance_horizon_spec##SUFFIX(    \
-        const SunskyKArgs* __restrict__ Kp, SeqIrradiance S, SeqIrrHorizon Z, const float* nx, const float* ny, \
-        const float* nz, const uint8_t* active, size_t n, float* out, size_t ostride) {                        \
-        seq_irradiance_body<false, true>(*Kp, S, nx, ny, nz, active, n, out, ostride, &Z);                     \
-    }
-SS_SEQUENCE_IRRADIANCE_HORIZON(_fast)
-SS_SEQUENCE_IRRADIANCE_HORIZON(_ref)
-
-// ======================================================================
-// Per-frame irradiance series (sunsky_sequence_prepare_irradiance_series / _irradiance_series; the
-// definition is in sunsky_amd.h): every frame's own E^k_p(n), bit for bit the irradiance of a
-// sequence that holds frame k alone with weight 1.  The frames are staged in groups
-// (sunsky_kernel_args.h): a group's image is the forward's image with G * P values per record,
-// so one clamped cosine per record and receiver pair is spent on G frames.
-// ======================================================================
-
-// A^k_p[i, j] = omega * sky_{k,p}(c_ij) into the groups' images, or sky_{k,p}(c_ij) of one frame
-// as a plain table.  One lane per (cell, group), the cell index fastest.  The sky is evaluated at
-// the cell centre as sunsky_sequence_irradiance_table computes it on the device; the record's
-// direction is the one prepare_irradiance staged from the host.  A frame's value is
-// seq_sky_sum's for a sequence of that frame alone with weight 1: fma(1, sky, 0), which gives a
-// negative zero the sign the weighted table gives it.
-extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_irradiance_series_table(
-    const SunskyKArgs* __restrict__ Kp, SeqArgs A, SeqIrrSeriesTableArgs T) {
-    const SunskyKArgs& K = *Kp;
-    const size_t cells = (size_t)T.nz * (size_t)T.nphi, n = cells * (size_t)T.groups;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const size_t cell = i % cells;
-        const int gr = (int)(i / cells);
-        const float3_ wo = seq_cell_centre(T.nz, T.nphi, (int)(cell / (size_t)T.nphi), (int)(cell % (size_t)T.nphi));
-        const SeqDir s = seq_dir<false>(wo, true);
-        float* rec = T.image ? T.image + ((size_t)gr * cells + cell) * (size_t)T.rec : nullptr;
-        if (rec) {   // the direction the forward's image holds (the host's), not this kernel's wo
-            const float* c = T.cells + cell * (size_t)T.cells_rec;
-            rec[0] = c[0]; rec[1] = c[1]; rec[2] = c[2];
-        }
-        auto put = [&](int g, int p, float sky) {
-            const float v = fmaf(1.f, sky, 0.f);
-            if (rec) rec[3 + g * T.planes + p] = T.omega * v;
-            else T.raw[(size_t)p * cells + cell] = v;
-        };
-#pragma unroll 1
-        for (int g = 0; g < T.group; ++g) {
-            const int k = T.frame0 + gr * T.group + g;
-            if (k >= A.count) break;   // past the last frame: the image's zeros stay
-            if (K.variant == kRGB) {
-                const int chans[3] = {0, 1, 2};
-                const SeqHot<false, 3> cur = seq_load<false, 3>(A.frames, 3, k, chans);
-                float v[3];
-                seq_sky_frame<true, 3>(K, cur, s, 0.f, v);
-#pragma unroll
-                for (int p = 0; p < 3; ++p) put(g, p, v[p]);
-            } else {
-#pragma unroll 1
-                for (int q = 0; q < T.planes; ++q) {
-                    const int lo = T.L.lo[q];
-                    const float f = T.L.f[q];
-                    float v[1] = {0.f};
-                    if (f >= 0.f) {
-                        const int chans[2] = {lo, lo + 1 < kNbWavelengths ? lo + 1 : lo};
-                        const SeqHot<false, 2> cur = seq_load<false, 2>(A.frames, kNbWavelengths, k, chans);
-                        seq_sky_frame<false, 2>(K, cur, s, f, v);
-                    }
-                    put(g, q, v[0]);
-                }
-            }
-        }
-    }
-}
-
-// The widest pass of the series' contraction in values (accumulator pairs per lane): 24 takes an
-// RGB group in one pass, 16 and 8 were measured against it (profiles/HISTORY.md).  A value's sum
-// does not depend on the pass it is in.
-#ifndef SS_SEQ_IRR_SERIES_PASS
-#define SS_SEQ_IRR_SERIES_PASS 24
-#endif
-
-// Work items are (tile of blockDim receiver pairs, group), grid-stride over both with the group
-// uniform over the workgroup: its records, suns and columns are read with one address per wave.
-// Per item and pass seq_irr_pass runs the sky of NP values over the group's image (no suns of
-// its own); then every value takes its frame's one sun, fma(cos, F_k[p], sum), under a horizon
-// when s_k.z >= h of the sun's sector; values outside the call's range of frames are not stored
-// and a pass without a value in range is skipped.
-template <bool RGB, bool HZ>
-__device__ __forceinline__ void seq_irr_series_body(const SunskyKArgs& K, const SeqIrrSeries& S, const float* nx,
-                                                    const float* ny, const float* nz, const uint8_t* active, size_t n,
-                                                    float* __restrict__ out, size_t ostride,
-                                                    const SeqIrrHorizon* Z = nullptr) {
-    const size_t pairs = (n + 1) / 2, tiles = (pairs + blockDim.x - 1) / blockDim.x;
-    const size_t items = tiles * (size_t)S.n_groups;
-    const int values = RGB ? 3 * seq_irr_series_group(3) : S.values;
-    const int rec = RGB ? seq_irr_record(3 * seq_irr_series_group(3)) : S.rec;
-    const seq_f2 zero = {0.f, 0.f};
-    for (size_t item = blockIdx.x; item < items; item += gridDim.x) {
-        const int gr = S.group0 + (int)(item / tiles);
-        const size_t t = (item % tiles) * blockDim.x + threadIdx.x;
-        if (t >= pairs) continue;
-        const size_t idx[2] = {t, t + pairs};
-        const bool has[2] = {true, idx[1] < n};
-        bool m[2];
-        float3_ nl[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const size_t i = has[h] ? idx[h] : t;
-            m[h] = !active || active[i] != 0;
-            nl[h] = to_local(K, mk3(nx[i], ny[i], nz[i]));
-        }
-        const seq_f2 lx = {nl[0].x, nl[1].x}, ly = {nl[0].y, nl[1].y}, lz = {nl[0].z, nl[1].z};
-        size_t e0 = 0, e1 = 0;
-        if constexpr (HZ) {
-            e0 = Z->per_receiver ? idx[0] : 0;
-            e1 = Z->per_receiver ? (has[1] ? idx[1] : idx[0]) : 0;
-        }
-        const SeqIrradiance C = {S.images + (size_t)gr * S.image_floats, nullptr, S.nz, S.nphi, 0, values};
-        const long long base = (long long)gr * values - S.plane0;   // the output plane of the group's value 0
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wold-style-cast"
-        seq_cfloat_p suns = (seq_cfloat_p)__builtin_assume_aligned(S.suns, 16) + (size_t)gr * values * 4;
-        seq_cint_p cols = (seq_cint_p)S.sun_cols + (size_t)gr * values;
-#pragma clang diagnostic pop
-        int p0 = 0;
-        auto pass = [&](auto np) {
-            constexpr int NP = decltype(np)::value;
-            const int q0 = p0;
-            p0 += NP;
-            if (base + q0 + NP <= 0 || base + q0 >= S.n_planes) return;
-            seq_f2 acc[NP];
-            seq_irr_pass<NP, RGB ? seq_irr_record(3 * seq_irr_series_group(3)) : 0, HZ>(C, rec, q0, lx, ly, lz, acc, Z, e0, e1);
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                seq_cfloat_p u = suns + (q0 + p) * 4;
-                seq_f2 c = __builtin_elementwise_max(seq_fma2(lz, u[2], seq_fma2(ly, u[1], lx * u[0])), zero);
-                if constexpr (HZ) {
-                    const float* hq = Z->h + (size_t)(cols[q0 + p] / Z->sector_len) * Z->stride;
-                    const float sz = u[2];
-                    c[0] = sz >= hq[e0] ? c[0] : 0.f;
-                    c[1] = sz >= hq[e1] ? c[1] : 0.f;
-                }
-                acc[p] = seq_fma2(c, u[3], acc[p]);
-                const long long plane = base + q0 + p;
-                if (plane < 0 || plane >= S.n_planes) continue;
-                float* o = out + (size_t)plane * ostride;
-                store_nt(m[0] ? acc[p][0] : 0.f, o + idx[0]);
-                if (has[1]) store_nt(m[1] ? acc[p][1] : 0.f, o + idx[1]);
-            }
-        };
-        if constexpr (RGB) {
-            constexpr int W = SS_SEQ_IRR_SERIES_PASS, rest = kSeqIrrSeriesWidth % W;
-            static_assert(rest == 0 || rest == 8, "an RGB group in passes of W values, then one of 8");
-#pragma unroll
-            for (int q = 0; q < kSeqIrrSeriesWidth / W; ++q) pass(std::integral_constant<int, W>());
-            if constexpr (rest == 8) pass(std::integral_constant<int, 8>());
-        } else {
-#pragma unroll 1
-            while (values - p0 >= SS_SEQ_IRR_SERIES_PASS) pass(std::integral_constant<int, SS_SEQ_IRR_SERIES_PASS>());
-            if constexpr (SS_SEQ_IRR_SERIES_PASS > 16)
-                if (values - p0 >= 16) pass(std::integral_constant<int, 16>());
-            if constexpr (SS_SEQ_IRR_SERIES_PASS > 8)
-                if (values - p0 >= 8) pass(std::integral_constant<int, 8>());
-            if (values - p0 >= 4) pass(std::integral_constant<int, 4>());
-            if (values - p0 >= 2) pass(std::integral_constant<int, 2>());
-            if (values - p0 >= 1) pass(std::integral_constant<int, 1>());
-        }
-    }
-}
-
-// Both precisions' names run the same body: the tables are reference precision by definition
-#define SS_SEQUENCE_IRRADIANCE_SERIES(SUFFIX)                                                                  \
-    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_irradiance_series_rgb##SUFFIX(      \
-        const SunskyKArgs* __restrict__ Kp, SeqIrrSeries S, const float* nx, const float* ny, const float* nz, \
-        const uint8_t* active, size_t n, float* out, size_t ostride) {                                         \
-        seq_irr_series_body<true, false>(*Kp, S, nx, ny, nz, active, n, out, ostride);                         \
-    }                                                                                                          \
-    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_irradiance_series_spec##SUFFIX(     \
-        const SunskyKArgs* __restrict__ Kp, SeqIrrSeries S, const float* nx, const float* ny, const float* nz, \
-        const uint8_t* active, size_t n, float* out, size_t ostride) {                                         \
-        seq_irr_series_body<false, false>(*Kp, S, nx, ny, nz, active, n, out, ostride);                        \
-    }                                                                                                          \
-    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_irradiance_series_horizon_rgb##SUFFIX( \
-        const SunskyKArgs* __restrict__ Kp, SeqIrrSeries S, SeqIrrHorizon Z, const float* nx, const float* ny, \
-        const float* nz, const uint8_t* active, size_t n, float* out, size_t ostride) {                        \
-        seq_irr_series_body<true, true>(*Kp, S, nx, ny, nz, active, n, out, ostride, &Z);                      \
-    }                                                                                                          \
-    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_irradiance_series_horizon_spec##SUFFIX( \
-        const SunskyKArgs* __restrict__ Kp, SeqIrrSeries S, SeqIrrHorizon Z, const float* nx, const float* ny, \
-        const float* nz, const uint8_t* active, size_t n, float* out, size_t ostride) {                        \
-        seq_irr_series_body<false, true>(*Kp, S, nx, ny, nz, active, n, out, ostride, &Z);                     \
-    }
-SS_SEQUENCE_IRRADIANCE_SERIES(_fast)
-SS_SEQUENCE_IRRADIANCE_SERIES(_ref)
-
-// ======================================================================
-// Gradients of the irradiance (sunsky_sequence_irradiance_vjp; the definition is in sunsky_amd.h).
-// Normals: seq_irr_pass's loop with the clamp's step in place of the clamp, one launch.  Weights:
-// the adjoint image (receivers streamed against the cells and suns a lane owns), then the fold.
-// ======================================================================
-
-// One pass over the staged image for a lane's two receivers: g_l = sum over records of
-// [n_l . d > 0] (sum_p d_out[p] value_p) d.  NP: the planes held in registers (RGB: 3; spectral:
-// the power of two at or above `planes`, the planes beyond it skipped by a wave-uniform test).
-// The order is the contract, seq_irr_pass's: a row's cells in column order into a row sum that
-// starts at 0, the row sums in row order, then the suns of the image; per record the plane fold
-// starts at 0 and runs in plane order; every product-and-add is one fma.
-template <bool RGB, int NP, int REC>
-__device__ __forceinline__ void seq_irr_vjp_pass(const SeqIrradiance& S, int rec, seq_f2 nx, seq_f2 ny, seq_f2 nz,
-                                                 const seq_f2 (&d)[NP], seq_f2 (&g)[3]) {
-    if constexpr (REC != 0) rec = REC;
-    const int planes = RGB ? 3 : S.planes;
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wold-style-cast"
-    seq_cfloat_p r = (seq_cfloat_p)__builtin_assume_aligned(S.cells, 16) + 3;
-    seq_cfloat_p u = (seq_cfloat_p)__builtin_assume_aligned(S.suns, 16) + 3;
-#pragma clang diagnostic pop
-    const seq_f2 zero = {0.f, 0.f};
-    auto add = [&](seq_cfloat_p q, seq_f2 (&sum)[3]) {
-        const seq_f2 dt = seq_fma2(nz, q[-1], seq_fma2(ny, q[-2], nx * q[-3]));
-        seq_f2 a = zero;
-#pragma unroll
-        for (int p = 0; p < NP; ++p)
-            if (RGB || p < planes) a = seq_fma2(d[p], q[p], a);
-        const seq_f2 m = {dt[0] > 0.f ? a[0] : 0.f, dt[1] > 0.f ? a[1] : 0.f};
-#pragma unroll
-        for (int c = 0; c < 3; ++c) sum[c] = seq_fma2(m, q[c - 3], sum[c]);
-    };
-#pragma unroll
-    for (int c = 0; c < 3; ++c) g[c] = zero;
-#pragma unroll 1
-    for (int i = 0; i < S.nz; ++i) {
-        seq_f2 row[3] = {zero, zero, zero};
-#pragma unroll 4
-        for (int j = 0; j < S.nphi; ++j, r += rec) add(r, row);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) g[c] += row[c];
-    }
-#pragma unroll 1
-    for (int k = 0; k < S.nsuns; ++k, u += rec) add(u, g);
-}
-
-// Two receivers per lane, as seq_irradiance_body pairs them; the masked cotangent of both in
-// registers (a masked lane's is 0 and its gradient is stored as exact zeros).
-template <bool RGB, int NP>
-__device__ __forceinline__ void seq_irr_vjp_normal_planes(const SunskyKArgs& K, const SeqIrradiance& S, const float* nx,
-                                                          const float* ny, const float* nz, const uint8_t* active,
-                                                          size_t n, const float* __restrict__ dout, size_t dstride,
-                                                          float* __restrict__ gx, float* __restrict__ gy,
-                                                          float* __restrict__ gz) {
-    const size_t stride = (size_t)gridDim.x * blockDim.x, pairs = (n + 1) / 2;
-    const int planes = RGB ? 3 : S.planes;
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < pairs; t += stride) {
-        const size_t idx[2] = {t, t + pairs};
-        const bool has[2] = {true, idx[1] < n};
-        bool m[2];
-        float3_ nl[2];
-        seq_f2 d[NP];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const size_t i = has[h] ? idx[h] : t;
-            m[h] = !active || active[i] != 0;
-            nl[h] = to_local(K, mk3(nx[i], ny[i], nz[i]));
-#pragma unroll
-            for (int p = 0; p < NP; ++p) d[p][h] = (RGB || p < planes) && m[h] ? dout[(size_t)p * dstride + i] : 0.f;
-        }
-        const seq_f2 lx = {nl[0].x, nl[1].x}, ly = {nl[0].y, nl[1].y}, lz = {nl[0].z, nl[1].z};
-        seq_f2 g[3];
-        seq_irr_vjp_pass<RGB, NP, RGB ? seq_irr_record(3) : 0>(S, seq_irr_record(planes), lx, ly, lz, d, g);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            if (!has[h]) continue;
-            const float3_ w = to_local_transposed(K, mk3(g[0][h], g[1][h], g[2][h]));
-            store_nt(m[h] ? w.x : 0.f, gx + idx[h]);
-            store_nt(m[h] ? w.y : 0.f, gy + idx[h]);
-            store_nt(m[h] ? w.z : 0.f, gz + idx[h]);
-        }
-    }
-}
-
-template <bool RGB>
-__device__ __forceinline__ void seq_irr_vjp_normal_body(const SunskyKArgs& K, const SeqIrradiance& S, const float* nx,
-                                                        const float* ny, const float* nz, const uint8_t* active, size_t n,
-                                                        const float* dout, size_t dstride, float* gx, float* gy,
-                                                        float* gz) {
-    if constexpr (RGB) {
-        seq_irr_vjp_normal_planes<true, 3>(K, S, nx, ny, nz, active, n, dout, dstride, gx, gy, gz);
-    } else {
-        if (S.planes <= 4) seq_irr_vjp_normal_planes<false, 4>(K, S, nx, ny, nz, active, n, dout, dstride, gx, gy, gz);
-        else if (S.planes <= 8) seq_irr_vjp_normal_planes<false, 8>(K, S, nx, ny, nz, active, n, dout, dstride, gx, gy, gz);
-        else if (S.planes <= 16) seq_irr_vjp_normal_planes<false, 16>(K, S, nx, ny, nz, active, n, dout, dstride, gx, gy, gz);
-        else seq_irr_vjp_normal_planes<false, kSeqIrrMaxPlanes>(K, S, nx, ny, nz, active, n, dout, dstride, gx, gy, gz);
-    }
-}
-
-// The adjoint image of one slice of receivers: per entry e (cell e < cells, else the sun of
-// frame e - cells) and plane p,  rows[slice][p][e] = sum over the slice's receivers of
-// d_out[p, r] max(0, n_l,r . dir_e).  Work item = (slice, tile of kSeqIrrGradTile entries, pass
-// of NP planes), grid-stride over the items: what an item computes does not depend on the grid.
-// A lane owns kSeqIrrGradCellsPerLane entries (e = tile start + c 256 + lane).  The receivers
-// are the streamed operand: a chunk of 256, one per lane -- n_l = to_local(n) (the forward's
-// bits) and the masked cotangent, all 0 for a masked lane -- goes to LDS once and every lane
-// reads it back with one address per wave (a broadcast).  Fixed order: a chunk's receivers in
-// index order into a chunk sum that starts at 0, the chunk sums in chunk order into the slice's
-// sum; the dot product is the forward's.
-template <bool RGB>
-__device__ __forceinline__ void seq_irr_adjoint_body(const SunskyKArgs& K, const SeqIrradiance& S, const SeqIrrGrad& G,
-                                                     const float* nx, const float* ny, const float* nz,
-                                                     const uint8_t* active, size_t n) {
-    constexpr int NP = RGB ? 3 : kSeqIrrGradSpecPlanes, CPL = kSeqIrrGradCellsPerLane;
-    static_assert(CPL % 2 == 0, "entries go in pairs");
-    static_assert(NP + 3 <= 8, "a receiver's LDS record is 8 floats");
-    __shared__ float4 sh[kSeqIrrGradChunk][2];   // {n_l.xyz, d[0]}, {d[1], d[2], d[3], -}
-    const int tid = threadIdx.x, planes = RGB ? 3 : S.planes, rec = seq_irr_record(planes);
-    const size_t cells = (size_t)S.nz * (size_t)S.nphi, entries = cells + (size_t)G.count;
-    const size_t tiles = (entries + kSeqIrrGradTile - 1) / kSeqIrrGradTile;
-    const size_t passes = (size_t)((planes + NP - 1) / NP);
-    const size_t items = (size_t)G.slices * tiles * passes;
-    for (size_t item = blockIdx.x; item < items; item += gridDim.x) {
-        const int p0 = (int)(item % passes) * NP;
-        const size_t tile = (item / passes) % tiles, slice = item / passes / tiles;
-        seq_f2 dx[CPL / 2], dy[CPL / 2], dz[CPL / 2];   // entries 2 c and 2 c + 1 share packed instructions
-        size_t e[CPL];
-#pragma unroll
-        for (int c = 0; c < CPL; ++c) {
-            e[c] = tile * kSeqIrrGradTile + (size_t)c * kSeqIrrGradChunk + (size_t)tid;
-            const size_t ec = e[c] < entries ? e[c] : 0;
-            const float* q = ec < cells ? S.cells + ec * (size_t)rec : G.suns + (ec - cells) * 4;
-            dx[c / 2][c % 2] = q[0];
-            dy[c / 2][c % 2] = q[1];
-            dz[c / 2][c % 2] = q[2];
-        }
-        const seq_f2 zero = {0.f, 0.f};
-        seq_f2 acc[CPL / 2][NP];
-#pragma unroll
-        for (int c = 0; c < CPL / 2; ++c)
-#pragma unroll
-            for (int p = 0; p < NP; ++p) acc[c][p] = zero;
-        const size_t r0 = slice * (size_t)G.slice_len, r1 = r0 + G.slice_len < n ? r0 + G.slice_len : n;
-#pragma unroll 1
-        for (size_t base = r0; base < r1; base += kSeqIrrGradChunk) {
-            __syncthreads();   // every lane is done with the previous chunk
-            const size_t i = base + (size_t)tid;
-            float3_ nl = mk3(0.f, 0.f, 0.f);
-            float d[4] = {0.f, 0.f, 0.f, 0.f};
-            if (i < r1 && (!active || active[i] != 0)) {
-                nl = to_local(K, mk3(nx[i], ny[i], nz[i]));
-#pragma unroll
-                for (int p = 0; p < NP; ++p)
-                    if (p0 + p < planes) d[p] = G.dout[(size_t)(p0 + p) * G.dstride + i];
-            }
-            sh[tid][0] = make_float4(nl.x, nl.y, nl.z, d[0]);
-            sh[tid][1] = make_float4(d[1], d[2], d[3], 0.f);
-            __syncthreads();
-            const int cnt = (int)(r1 - base < (size_t)kSeqIrrGradChunk ? r1 - base : (size_t)kSeqIrrGradChunk);
-            seq_f2 part[CPL / 2][NP];
-#pragma unroll
-            for (int c = 0; c < CPL / 2; ++c)
-#pragma unroll
-                for (int p = 0; p < NP; ++p) part[c][p] = zero;
-#pragma unroll 4
-            for (int j = 0; j < cnt; ++j) {
-                const float4 a = sh[j][0], b = sh[j][1];
-                const float dj[4] = {a.w, b.x, b.y, b.z};
-#pragma unroll
-                for (int c = 0; c < CPL / 2; ++c) {
-                    const seq_f2 cs =
-                        __builtin_elementwise_max(seq_fma2(dz[c], a.z, seq_fma2(dy[c], a.y, dx[c] * a.x)), zero);
-#pragma unroll
-                    for (int p = 0; p < NP; ++p) part[c][p] = seq_fma2(cs, dj[p], part[c][p]);
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < CPL / 2; ++c)
-#pragma unroll
-                for (int p = 0; p < NP; ++p) acc[c][p] += part[c][p];
-        }
-#pragma unroll
-        for (int c = 0; c < CPL; ++c)
-#pragma unroll
-            for (int p = 0; p < NP; ++p)
-                if (e[c] < entries && p0 + p < planes)
-                    G.rows[(slice * (size_t)planes + (size_t)(p0 + p)) * entries + e[c]] = acc[c / 2][p][c % 2];
-    }
-}
-
-// Phase 0: rows[0] = ((rows[0] + rows[1]) + rows[2]) + ..., the slices in slice order, one
-// element per lane.  Phase 1, one workgroup per frame k (grid-stride over the frames):
-//   grad_weight[k] += omega sum_p sum_ij G_p[i, j] sky_{k,p}(c_ij) + sum_p H_p[k] F_k[p]
-// with sky_{k,p} from seq_sky_frame (the table kernels' frame body).  Fixed shape: a lane adds
-// its cells (cell = lane + 256 t, t ascending) into one sum that starts at 0 -- RGB: a cell's
-// three planes in plane order; spectral: plane by plane, an invalid wavelength skipped -- every
-// step fma(G, sky, sum); then wave_sum's tree, the 4 waves in wave order, times omega; then the
-// sun sum, fma(H_p[k], F_k[p], h) from 0 in plane order, added once.  A frame whose sun is
-// below the horizon is left alone (+= exactly 0).
-__device__ __forceinline__ void seq_irr_grad_fold_body(const SunskyKArgs& K, const SeqArgs& A, const SeqIrradiance& S,
-                                                       const SeqIrrGrad& G, const LambdaSet& L, int phase,
-                                                       float* __restrict__ grad_weight) {
-    const int planes = S.planes;
-    const size_t cells = (size_t)S.nz * (size_t)S.nphi, entries = cells + (size_t)G.count;
-    if (phase == 0) {
-        const size_t total = (size_t)planes * entries, stride = (size_t)gridDim.x * blockDim.x;
-        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-            float v = G.rows[i];
-#pragma unroll 1
-            for (unsigned s = 1; s < G.slices; ++s) v += G.rows[(size_t)s * total + i];
-            G.rows[i] = v;
-        }
-        return;
-    }
-    __shared__ float red[SS_BLOCK / 64];
-    const int tid = threadIdx.x;
-    for (int k = blockIdx.x; k < G.count; k += gridDim.x) {
-        seq_cfloat_p rec = seq_record(A.frames, K.nch, k);
-        if (!(rec[2] >= 0.f)) continue;   // wave-uniform: the whole workgroup skips a night frame
-        float sum = 0.f;
-        if (K.variant == kRGB) {
-            const int chans[3] = {0, 1, 2};
-            const SeqHot<false, 3> cur = seq_load<false, 3>(A.frames, 3, k, chans);
-            for (size_t cell = (size_t)tid; cell < cells; cell += SS_BLOCK) {
-                const float3_ wo = seq_cell_centre(S.nz, S.nphi, (int)(cell / (size_t)S.nphi), (int)(cell % (size_t)S.nphi));
-                float v[3];
-                seq_sky_frame<true, 3>(K, cur, seq_dir<false>(wo, true), 0.f, v);
-#pragma unroll
-                for (int p = 0; p < 3; ++p) sum = fmaf(G.rows[(size_t)p * entries + cell], v[p], sum);
-            }
-        } else {
-#pragma unroll 1
-            for (int q = 0; q < planes; ++q) {
-                const int lo = L.lo[q];
-                const float f = L.f[q];
-                if (!(f >= 0.f)) continue;
-                const int chans[2] = {lo, lo + 1 < kNbWavelengths ? lo + 1 : lo};
-                const SeqHot<false, 2> cur = seq_load<false, 2>(A.frames, kNbWavelengths, k, chans);
-                for (size_t cell = (size_t)tid; cell < cells; cell += SS_BLOCK) {
-                    const float3_ wo = seq_cell_centre(S.nz, S.nphi, (int)(cell / (size_t)S.nphi), (int)(cell % (size_t)S.nphi));
-                    float v[1];
-                    seq_sky_frame<false, 2>(K, cur, seq_dir<false>(wo, true), f, v);
-                    sum = fmaf(G.rows[(size_t)q * entries + cell], v[0], sum);
-                }
-            }
-        }
-        const float w = wave_sum(sum);
-        __syncthreads();   // red[] of the previous frame has been read
-        if ((tid & 63) == 0) red[tid >> 6] = w;
-        __syncthreads();
-        if (tid == 0) {
-            float t = red[0];
-#pragma unroll
-            for (int i = 1; i < SS_BLOCK / 64; ++i) t += red[i];
-            float h = 0.f;
-#pragma unroll 1
-            for (int p = 0; p < planes; ++p) h = fmaf(G.rows[(size_t)p * entries + cells + (size_t)k], G.flux[(size_t)p * G.count + k], h);
-            grad_weight[k] += G.omega * t + h;
-        }
-    }
-}
-
-// Both precisions' names run the same bodies, as the forward's do
-#define SS_SEQUENCE_IRRADIANCE_GRAD(SUFFIX)                                                                    \
-    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_irradiance_vjp_normal_rgb##SUFFIX(  \
-        const SunskyKArgs* __restrict__ Kp, SeqIrradiance S, const float* nx, const float* ny, const float* nz, \
-        const uint8_t* active, size_t n, const float* dout, size_t dstride, float* gx, float* gy, float* gz) { \
-        seq_irr_vjp_normal_body<true>(*Kp, S, nx, ny, nz, active, n, dout, dstride, gx, gy, gz);               \
-    }                                                                                                          \
-    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_irradiance_vjp_normal_spec##SUFFIX( \
-        const SunskyKArgs* __restrict__ Kp, SeqIrradiance S, const float* nx, const float* ny, const float* nz, \
-        const uint8_t* active, size_t n, const float* dout, size_t dstride, float* gx, float* gy, float* gz) { \
-        seq_irr_vjp_normal_body<false>(*Kp, S, nx, ny, nz, active, n, dout, dstride, gx, gy, gz);              \
-    }                                                                                                          \
-    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_irradiance_adjoint##SUFFIX(         \
-        const SunskyKArgs* __restrict__ Kp, SeqIrradiance S, SeqIrrGrad G, const float* nx, const float* ny,   \
-        const float* nz, const uint8_t* active, size_t n) {                                                    \
-        if (Kp->variant == kRGB) seq_irr_adjoint_body<true>(*Kp, S, G, nx, ny, nz, active, n);                 \
-        else seq_irr_adjoint_body<false>(*Kp, S, G, nx, ny, nz, active, n);                                    \
-    }                                                                                                          \
-    extern "C" __global__ __launch_bounds__(SS_BLOCK) void sunsky_sequence_irradiance_grad_fold##SUFFIX(       \
-        const SunskyKArgs* __restrict__ Kp, SeqArgs A, SeqIrradiance S, SeqIrrGrad G, LambdaSet L, int phase,  \
-        float* grad_weight) {                                                                                  \
-        seq_irr_grad_fold_body(*Kp, A, S, G, L, phase, grad_weight);                                           \
-    }
-SS_SEQUENCE_IRRADIANCE_GRAD(_fast)
-SS_SEQUENCE_IRRADIANCE_GRAD(_ref)
-
-// Batched staging of a sequence's records: workgroup = frame, sunsky_stage_radiance's sky part
-// (radiance_param per entry, then one thread per channel folds it) from the RadianceStage
-// scalars the host put into the record's header.  No sun table: see seq_disc_*.
-extern "C" __global__ __launch_bounds__(256) void sunsky_stage_sequence(SeqStageArgs A) {
-    __shared__ float p[kNbWavelengths * kNbSkyParams];
-    __shared__ float r[kNbWavelengths];
-    const int t = threadIdx.x;
-    const int np = A.nch * kNbSkyParams;
-    const size_t rec_bytes = kSeqFrameHeader + (size_t)A.nch * (sizeof(FastChannel) + sizeof(SkyChannel));
-    for (int fr = blockIdx.x; fr < A.count; fr += gridDim.x) {
-        char* rec = static_cast<char*>(A.frames) + (size_t)fr * rec_bytes;
-        const SeqFrame<1>* h = reinterpret_cast<const SeqFrame<1>*>(rec);   // the header is the same for every NCH
-        RadianceStage rs;
-        rs.x = h->x;
-        rs.t_rem = h->t_rem;
-        rs.t_low = h->t_low;
-        rs.t_high = h->t_high;
-        rs.in_range = h->in_range;
-        for (int e = t; e < np; e += blockDim.x)
-            p[e] = radiance_param(A.sky_params_ds, np, e, rs, A.albedo[e / kNbSkyParams]);
-        for (int e = t; e < A.nch; e += blockDim.x) r[e] = radiance_param(A.sky_rad_ds, A.nch, e, rs, A.albedo[e]);
-        __syncthreads();
-        if (t < A.nch) {
-            SkyChannel ch;
-            FastChannel f;
-            fold_channel(&p[t * kNbSkyParams], r[t], A.variant, A.sky_scale, &ch, &f);
-            reinterpret_cast<FastChannel*>(rec + kSeqFrameHeader)[t] = f;
-            reinterpret_cast<SkyChannel*>(rec + kSeqFrameHeader + (size_t)A.nch * sizeof(FastChannel))[t] = ch;
-        }
-        __syncthreads();
-    }
-}
-
-// Batched staging of a sequence's gradient records (sunsky_sequence_prepare_grad / _update):
-// workgroup = frame, one thread per entry of the two sky blocks, each tangent_value in fp64
-// (the function sunsky_stage_tangent runs) with the frame's TangentStage scalars from the
-// host: the turbidity tangent (dT = 1) and the unit-elevation tangent (dx = dx / d eta).  The
-// host has written dlocal / deta; the blocks' padding is written 0.
-extern "C" __global__ __launch_bounds__(256) void sunsky_stage_sequence_grad(SeqGradStageArgs A) {
-    __shared__ TangentStage sh[2];
-    const int block = seq_grad_block(A.nch), rec = 2 * block + 12;
-    for (int fr = blockIdx.x; fr < A.count; fr += gridDim.x) {
-        float* g = static_cast<float*>(A.grads) + (size_t)fr * rec;
-        if (threadIdx.x < 2) {   // the two tangents in LDS: their albedo is indexed per entry
-            TangentStage s = A.stages[fr];
-            if (threadIdx.x == 0) s.dT = 1.0;
-            else s.dx = s.dx_per_eta;
-            sh[threadIdx.x] = s;
-        }
-        __syncthreads();
-        for (int j = threadIdx.x; j < 2 * block; j += blockDim.x) {
-            const int e = j % block;
-            g[j] = e < A.nch * 10 ? tangent_value(A.sky_params_ds, A.sky_rad_ds, sh[j < block ? 0 : 1], e) : 0.f;
-        }
-        __syncthreads();
-    }
-}
+// The families below are parts of this translation unit (DESIGN.md "Kernel source map"), included once each,
+// in order; a new family goes into a part of its own under kernels/, not onto the end of this file.
+#include "kernels/staging.h"                    // device staging of parameters_changed: sunsky_stage_radiance / tangent / quad_*
+#include "kernels/sequence.h"                   // frame sequences: the weighted sum of K frames' eval and bake, helpers the later parts share; staging of the records
+#include "kernels/sequence_grad.h"              // frame sequences: per-frame gradients of the weighted sum; staging of their records
+#include "kernels/sequence_sampling.h"          // frame sequences: importance sampling, its sky table and sun list
+#include "kernels/sequence_irradiance.h"        // frame sequences: irradiance on oriented receivers, with or without a horizon profile
+#include "kernels/sequence_irradiance_series.h" // frame sequences: the per-frame irradiance series
+#include "kernels/sequence_irradiance_grad.h"   // frame sequences: gradients of the irradiance (receiver normals, frame weights)

@@ -1,6 +1,6 @@
 // sunsky_staging.h -- the per-entry arithmetic of the emitter's parameter staging,
 // shared by the host model (sunsky_model.cpp: host-only emitters, the CPU tests)
-// and the device staging kernels (sunsky_kernels.hip: parameters_changed of a GPU
+// and the device staging kernels (kernels/staging.h: parameters_changed of a GPU
 // emitter, stream-ordered).  One definition, one operation order, contraction off:
 // the polynomial staging (compute_radiance_params, compute_sun_params, the channel
 // folding) is bitwise the same on both sides.  The host computes the few libm

@@ -2,7 +2,9 @@
 
 usage: python tools/isa_summary.py KERNEL.s NAME [NAME ...]
 (make the listing with: hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S
- -I include -I mitsuba3-sunsky_amd/csrc -o KERNEL.s mitsuba3-sunsky_amd/csrc/sunsky_kernels.hip)
+ -I include -I mitsuba3-sunsky_amd/csrc -o KERNEL.s mitsuba3-sunsky_amd/csrc/sunsky_kernels.hip;
+ sunsky_kernels.hip is the one translation unit, its parts are csrc/kernels/*.h;
+ tools/isa_diff.py compares two such listings kernel by kernel)
 
 Prints, per kernel: instruction count by class (VALU / transcendental / SALU / LDS /
 global / branch), the most frequent opcodes, and the register/LDS/spill metadata.

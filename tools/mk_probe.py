@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Probe builds of the product kernels, made OUTSIDE the product source.
 
-The shipped `mitsuba3-sunsky_amd/csrc/sunsky_kernels.hip` holds no probe code.  A probe
-(cost ablation, compute-only build, layout experiment) is a list of textual edits applied
-here to a copy of it in tools/build/, which is then compiled to tools/build/probe_<name>.hsaco
+The shipped `mitsuba3-sunsky_amd/csrc/sunsky_kernels.hip` and its parts (`csrc/kernels/*.h`)
+hold no probe code.  A probe (cost ablation, compute-only build, layout experiment) is a list
+of textual edits applied here to a copy of the source in tools/build/ (one file: the parts
+expanded in place of their #include lines), which is then compiled to tools/build/probe_<name>.hsaco
 for tools/gpu_ab.sh / kbench.  An edit whose anchor is missing fails loudly, so a probe
 never silently measures the unmodified product.  Probes whose anchors a later change removed
 are dropped from the table (their A/B logs stay in profiles/, their edits in git history).
@@ -12,6 +13,7 @@ usage: python tools/mk_probe.py <name> [--src FILE]   (tools/Makefile: make buil
 """
 import argparse
 import os
+import re
 import subprocess
 import sys
 
@@ -121,10 +123,8 @@ PROBES = {
     # the general RGB call (kSortPos) with the hoisted sun rows, held to 4 waves/SIMD
     "pos_hoist": [
         ("""    constexpr bool kHoist = MODE == kSortLean;""", """    constexpr bool kHoist = MODE != kSortFull;"""),
-        ("""#ifndef SS_RGB_SORTED_ATTR   // probe builds (tools/build) set occupancy attributes here
-#define SS_RGB_SORTED_ATTR
-""", """#ifndef SS_RGB_SORTED_ATTR   // probe builds (tools/build) set occupancy attributes here
-#define SS_RGB_SORTED_ATTR __attribute__((amdgpu_waves_per_eu(4)))
+        ("""#define SS_RGB_SORTED_ATTR
+""", """#define SS_RGB_SORTED_ATTR __attribute__((amdgpu_waves_per_eu(4)))
 """),
     ],
     # the RGB eval in span_steps form (measured 4 % slower at 16M; the product keeps grid-stride)
@@ -143,8 +143,15 @@ PROBES = {
 }
 
 
+def product_source(src_path):
+    """The product source as one text: the top file with its parts (kernels/*.h) in place."""
+    src_dir = os.path.dirname(os.path.abspath(src_path))
+    return re.sub(r'^#include "(kernels/[\w.]+)".*\n', lambda m: open(os.path.join(src_dir, m.group(1))).read(),
+                  open(src_path).read(), flags=re.M)
+
+
 def make_source(name, src_path):
-    text = open(src_path).read()
+    text = product_source(src_path)
     for anchor, repl in PROBES[name]:
         if text.count(anchor) != 1:
             sys.exit(f"mk_probe: probe '{name}': anchor found {text.count(anchor)} times (want 1):\n{anchor}")
