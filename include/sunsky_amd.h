@@ -21,7 +21,7 @@
  *     eval_jvp_dir, eval_vjp_dir, sequence_eval, sequence_sample_direction,
  *     sequence_pdf_direction, sequence_eval_vjp, sequence_irradiance,
  *     sequence_irradiance_horizon, sequence_irradiance_vjp,
- *     sequence_irradiance_series)
+ *     sequence_irradiance_horizon_vjp, sequence_irradiance_series)
  *     allocate nothing, make no host-synchronous call and may be captured into
  *     a hipGraph (tests/test_graph_capture.py).  Kernels read the emitter state
  *     from device memory, which parameters_changed_async rewrites in place on
@@ -573,7 +573,7 @@ int sunsky_sequence_irradiance(const sunsky_sequence *seq, sunsky_vec3_in normal
  * does not depend on n, on the grid or on the lane; a shared profile gives the bits of the same
  * profile repeated per receiver.
  *
- * Out of scope: gradients under a horizon (sunsky_sequence_irradiance_vjp is the unoccluded one),
+ * Out of scope (the gradients are sunsky_sequence_irradiance_horizon_vjp's, below):
  * partial shading of a sun disc, near-field or per-cell visibility bitmaps, ground reflection,
  * and profiles whose H does not divide n_phi (the caller picks n_phi: 240 for 48 sectors).
  *
@@ -707,9 +707,10 @@ int sunsky_sequence_irradiance_series(const sunsky_sequence *seq, sunsky_vec3_in
  * additions (chunk, chunks, slices, lane, tree 6 + waves 3 + omega and h 2, suns).
  *
  * sunsky_sequence_prepare_irradiance_grad (host-synchronous; needs prepare_irradiance first)
- * stages on the device what the forward's image lacks -- every frame's local sun direction and
- * the unweighted F_k[p] -- and allocates the reduction workspace: at most 64 rows of P (Q + K)
- * floats and at most 2^22 floats (16 MiB), or one row where that is more.  The environment
+ * stages on the device what the forward's image lacks -- every frame's local sun direction, the
+ * unweighted F_k[p] and every frame's sun column j_k -- and allocates the reduction workspace:
+ * at most 64 rows of P (Q + K) floats and at most 2^22 floats (16 MiB), or one row where that is
+ * more.  The environment
  * variable SUNSKY_AMD_IRRADIANCE_GRAD_WORKSPACE_FLOATS, read at prepare time, lowers the 2^22.
  * It is sticky: once called, a later prepare_irradiance restages it for the new tables;
  * sunsky_sequence_update drops it together with the tables (prepare_irradiance brings both back).
@@ -725,6 +726,75 @@ int sunsky_sequence_prepare_irradiance_grad(sunsky_sequence *seq);
 int sunsky_sequence_irradiance_vjp(const sunsky_sequence *seq, sunsky_vec3_in normal, const uint8_t *active,
                                    size_t n, const float *d_out, size_t d_stride, sunsky_vec3_out grad_normal,
                                    float *grad_weight, void *stream);
+
+/* Gradients of the irradiance under a horizon profile (reverse mode): with respect to the receiver
+ * normals, the frame weights and the profile itself.  Additive: sunsky_sequence_irradiance_vjp and
+ * its bits are untouched.  Notation is that of sunsky_sequence_irradiance_horizon and of
+ * sunsky_sequence_irradiance_vjp: A_p = fp32(omega R_p) and B_k[p] = fp32(w_k F_k[p]) the staged
+ * image's values, n_l = to_local(n), t_r[i, b] = fma(-h_r[b], (float)n_z, (float)(i + 1)),
+ * v = min(max(t, 0), 1), dot the forward's fma(z, z, fma(y, y, x x)), a_r and b_r
+ * sunsky_sequence_irradiance_vjp's plane folds (from 0, in plane order), and
+ *     L = sum_r sum_p d_out[p, r] E_p(n_r; h_r).
+ *
+ * Normal gradient: written, world space, three planes.
+ *     g_l(r) = sum_ij m_r[i, j] c_ij + sum_k [s_k.z >= h_r[b_k]] [n_l . s_k > 0] b_r[k] s_k,
+ *     m_r[i, j] = [n_l . c_ij > 0] ? fp32(a_r[i, j] v_r[i, b(j)]) : 0,
+ *     grad_normal(r) = (to_local's linear part)^T g_l(r).
+ * The step is strict; the sun's visibility is the forward's exact fp32 comparison.  Summation
+ * order: sunsky_sequence_irradiance_vjp's (a row's cells in column order into a row sum from 0,
+ * the rows in row order, then the image's suns in frame order, every product-and-add one fma);
+ * the only addition is the rounded a v.
+ *
+ * Weight gradient: accumulated (+=), every frame counts (a zero-weight one included).
+ *     grad_weight[k] += sum_r sum_p d_out[p, r] E^k_p(n_r; h_r),
+ *     E^k_p(n; h) = sum_ij omega sky_{k,p}(c_ij) fp32(max(0, dot) v) + [s_k.z >= h[b_k]] F_k[p] max(0, n_l . s_k),
+ * the series' per-frame irradiance under a horizon.  It goes through the adjoint image
+ *     G_p[i, j] = sum_r d_out[p, r] fp32(max(0, dot) v_r[i, b(j)]),
+ *     H_p[k]    = sum_r d_out[p, r] [s_k.z >= h_r[b_k]] max(0, dot)     for all K frames,
+ * b_k from every frame's column j_k, and then through sunsky_sequence_irradiance_vjp's fold,
+ * unchanged.  The reduction shape is exactly sunsky_sequence_irradiance_vjp's (slices, chunks of
+ * 256 receivers in index order, slice order, the per-frame fold): a function of (n, P, Q, K) and
+ * the workspace bound alone, deterministic, no float atomics; which lane or workgroup owns an
+ * entry does not enter the bits (H and the profile's layout do not change the shape either).
+ *
+ * Horizon gradient: written, one value per (sector, receiver) at
+ * grad_horizon[b * grad_horizon_stride + r], also for a shared profile (n_profiles = 1): the call
+ * does no reduction over receivers, and the caller sums the columns for a shared profile.
+ *     dE/dh_r[b] = -(float)n_z sum_i [0 < t_r[i, b] < 1] sum_{j in b} max(0, n_l . c_ij) a_r[i, j].
+ * The visible share is linear in h, so E is piecewise linear in h.  In fp32 at most one row per
+ * sector has 0 < t < 1 (t_i < 1 implies the exact x + i + 1 < 1, so with t_i > 0 the exact
+ * x + i + 2 > 1 and t_{i+1} >= 1): the value is that row's sector cells in column order,
+ * s = fma(max(0, dot), a, s) from 0, then s (-(float)n_z); +0 when no row is partly covered.  The
+ * sun is a point source: its visibility is a step and contributes no horizon gradient.
+ *
+ * Consequences.  h <= 0 in every sector (0, -0, -1): grad_normal and grad_weight are bit for bit
+ * sunsky_sequence_irradiance_vjp's, grad_horizon is exact zeros.  h > 1 in every sector:
+ * grad_normal and grad_horizon are exact zeros, grad_weight is left bit for bit as it was.  A shared
+ * profile gives the bits of the same profile repeated per receiver, for all three outputs.
+ * Inactive lanes write exact zeros to grad_normal and grad_horizon and add exactly 0 to the
+ * weights.  A NaN in a profile is unspecified for that receiver's grad_normal and grad_horizon
+ * only, and for the whole grad_weight.  The result does not depend on n, the grid, the lane or
+ * SUNSKY_AMD_BLOCKS_PER_CU.
+ *
+ * There is no new prepare call: sunsky_sequence_prepare_irradiance_grad additionally stages every
+ * frame's sun column j_k on the device, under its sticky / restage / update rules.  The call
+ * shares sunsky_sequence_irradiance_vjp's workspace; ordering calls on one sequence across
+ * streams is the caller's job.
+ *
+ * A hot-path call: stream-ordered, no allocation, no host-synchronous call, capturable.  Any
+ * output may be NULL (grad_normal: all three planes).  n == 0 succeeds and writes nothing (nothing
+ * else is looked at); n <= 2^32 - 256.  Refused with SUNSKY_ERROR_INVALID_VALUE and a message, in
+ * this order: a NULL normal or d_out; a partly NULL grad_normal; n > 2^32 - 256; a NULL horizon;
+ * n_sectors < 1; n_profiles other than 1 and n; horizon_stride < n with n_profiles == n and
+ * n_sectors > 1; grad_horizon_stride < n with n_sectors > 1 and a grad_horizon; a sequence without
+ * prepare_irradiance or prepare_irradiance_grad (the message names the missing call); n_sectors
+ * not a divisor of n_phi; a host-only sequence, as for the other launches; d_stride < n with more
+ * than one plane. */
+int sunsky_sequence_irradiance_horizon_vjp(const sunsky_sequence *seq, sunsky_vec3_in normal, const float *horizon,
+                                           int n_sectors, size_t n_profiles, size_t horizon_stride,
+                                           const uint8_t *active, size_t n, const float *d_out, size_t d_stride,
+                                           sunsky_vec3_out grad_normal, float *grad_weight, float *grad_horizon,
+                                           size_t grad_horizon_stride, void *stream);
 
 /* A caller of sample_direction / pdf_direction / eval: the sun-and-sky light a
  * smooth-diffuse point receives, gathered as the path integrator does at one vertex

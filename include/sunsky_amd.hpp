@@ -525,6 +525,22 @@ public:
                                              sunsky_vec3_out{grad_normal.x, grad_normal.y, grad_normal.z}, grad_weight,
                                              stream));
     }
+    // The same under a horizon profile (irradiance_horizon's profile arguments), and the gradient
+    // with respect to the profile: grad_horizon, written, one value per (sector, receiver) at
+    // grad_horizon + b * grad_horizon_stride + r (0: n), also for a shared profile -- the caller
+    // sums its columns.  Any output may be left out.  Needs prepare_irradiance_grad.
+    void irradiance_horizon_vjp(Vector3 normal, size_t n, const float* horizon, int n_sectors, bool per_receiver,
+                                const float* d_out, const Vector3Out& grad_normal, float* grad_weight, float* grad_horizon,
+                                const uint8_t* active = nullptr, size_t horizon_stride = 0, size_t d_stride = 0,
+                                size_t grad_horizon_stride = 0, void* stream = nullptr) const {
+        check(sunsky_sequence_irradiance_horizon_vjp(s_, sunsky_vec3_in{normal.x, normal.y, normal.z}, horizon, n_sectors,
+                                                     per_receiver ? n : 1,
+                                                     horizon_stride ? horizon_stride : per_receiver ? n : 1, active, n,
+                                                     d_out, d_stride ? d_stride : n,
+                                                     sunsky_vec3_out{grad_normal.x, grad_normal.y, grad_normal.z},
+                                                     grad_weight, grad_horizon,
+                                                     grad_horizon_stride ? grad_horizon_stride : n, stream));
+    }
     // Per-frame gradients of the weighted sum (sunsky_amd.h).  update: empty = keep the current
     // values; the frame count does not change.
     struct FrameTangent {

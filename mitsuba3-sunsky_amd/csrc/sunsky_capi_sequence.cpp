@@ -66,8 +66,9 @@ struct sunsky_sequence {
     // gradients of the irradiance (prepare_irradiance_grad): asked for once (sticky: a later
     // prepare_irradiance restages it), staged for the current tables when irr_grad_ready
     bool irr_grad_wanted = false, irr_grad_ready = false;
-    DeviceBuffer<float> d_irr_grad;          // every frame's sun | F_k[p] | the reduction workspace
+    DeviceBuffer<float> d_irr_grad;          // every frame's sun | F_k[p] | every frame's sun column | the reduction workspace
     SeqIrrGrad irr_grad = {};
+    const int* d_irr_grad_cols = nullptr;    // the column j_k of all K frames (irradiance_horizon_vjp's adjoint)
     size_t irr_grad_cap = 0;                 // the workspace bound in floats, as read at prepare time
     // the per-frame series (prepare_irradiance_series): sticky as the gradients are; the groups'
     // images, then the values' sun records, then their sun columns in one block
@@ -596,8 +597,9 @@ size_t seq_irr_grad_cap() {
 }
 
 // What sunsky_sequence_irradiance_vjp reads beside the forward's image, for the tables as they
-// are now: every frame's local sun direction, the unweighted fluxes, and the workspace of the
-// most slices the bound allows.  A host-only sequence only changes state.
+// are now: every frame's local sun direction, the unweighted fluxes, every frame's sun column
+// (sunsky_sequence_irradiance_horizon_vjp's sectors) and the workspace of the most slices the
+// bound allows.  A host-only sequence only changes state.
 void seq_stage_irradiance_grad(sunsky_sequence* q) {
     q->irr_grad_ready = false;
     if (q->device >= 0) {
@@ -606,13 +608,15 @@ void seq_stage_irradiance_grad(sunsky_sequence* q) {
         const size_t cells = (size_t)q->irr_nz * (size_t)q->irr_nphi, entries = cells + (size_t)count;
         q->irr_grad_cap = seq_irr_grad_cap();
         const size_t slices = seq_irr_grad_max_slices(planes, cells, count, q->irr_grad_cap);
-        const size_t head = 4 * (size_t)count + (size_t)planes * count;
+        static_assert(sizeof(int) == sizeof(float), "the suns' columns lie between the fluxes and the workspace");
+        const size_t cols_at = 4 * (size_t)count + (size_t)planes * count, head = cols_at + (size_t)count;
         std::vector<float> h(head, 0.f);
         for (int k = 0; k < count; ++k) {
             const SeqFrame<1>* f = seq_header(q, k);
             for (int a = 0; a < 3; ++a) h[4 * (size_t)k + a] = f->sun_n[a];
         }
         std::copy(q->irr_flux.begin(), q->irr_flux.end(), h.begin() + 4 * (size_t)count);
+        std::memcpy(h.data() + cols_at, q->irr_sun_cols.data(), sizeof(int) * (size_t)count);
         q->d_irr_grad.alloc(head + slices * planes * entries);
         hip_check(hipMemcpy(q->d_irr_grad.get(), h.data(), sizeof(float) * head, hipMemcpyHostToDevice), "hipMemcpy");
         SeqIrrGrad& g = q->irr_grad;
@@ -620,6 +624,7 @@ void seq_stage_irradiance_grad(sunsky_sequence* q) {
         g.suns = q->d_irr_grad.get();
         g.flux = q->d_irr_grad.get() + 4 * (size_t)count;
         g.rows = q->d_irr_grad.get() + head;
+        q->d_irr_grad_cols = reinterpret_cast<const int*>(q->d_irr_grad.get() + cols_at);
         g.omega = q->irr_omega;
         g.count = count;
     }
@@ -1402,6 +1407,66 @@ int sunsky_sequence_irradiance_vjp(const sunsky_sequence* seq, sunsky_vec3_in nr
         {   // one workgroup per work item (slice, tile, pass), grid-stride over the items
             void* args[] = {&lc.K, &S, &G, (void*)&nrm.x, (void*)&nrm.y, (void*)&nrm.z, &active, &n};
             lc.run(K_SEQUENCE_IRRADIANCE_ADJOINT, (size_t)shape.slices * tiles * passes * kBlock, args);
+        }
+        SeqArgs A = seq->args();
+        LambdaSet L = seq->irr_L;
+        for (int phase = shape.slices > 1 ? 0 : 1; phase < 2; ++phase) {
+            void* args[] = {&lc.K, &A, &S, &G, &L, &phase, &grad_weight};
+            lc.run(K_SEQUENCE_IRRADIANCE_GRAD_FOLD, phase == 0 ? (size_t)seq->irr_planes * entries : (size_t)seq->count * kBlock,
+                   args);
+        }
+    });
+}
+
+int sunsky_sequence_irradiance_horizon_vjp(const sunsky_sequence* seq, sunsky_vec3_in nrm, const float* horizon, int n_sectors,
+                                           size_t n_profiles, size_t hstride, const uint8_t* active, size_t n,
+                                           const float* d_out, size_t d_stride, sunsky_vec3_out grad_normal,
+                                           float* grad_weight, float* grad_horizon, size_t ghstride, void* stream) {
+    SUNSKY_PHASE("EndpointEvaluate", "sequence_irradiance_horizon_vjp");
+    if (!seq) return fail(SUNSKY_ERROR_INVALID_VALUE, "null sequence");
+    if (n == 0) return SUNSKY_OK;
+    if (!nrm.x || !nrm.y || !nrm.z || !d_out) return fail(SUNSKY_ERROR_INVALID_VALUE, "null normal / d_out pointer");
+    if (int rc = check_optional_vec3(grad_normal, "grad_normal")) return rc;
+    if (n > 0xffffff00ull) return fail(SUNSKY_ERROR_INVALID_VALUE, "more than 2^32 - 256 receivers");
+    if (!horizon) return fail(SUNSKY_ERROR_INVALID_VALUE, "null horizon pointer");
+    if (n_sectors < 1) return fail(SUNSKY_ERROR_INVALID_VALUE, "n_sectors must be >= 1 and divide the irradiance tables' n_phi");
+    if (n_profiles != 1 && n_profiles != n) return fail(SUNSKY_ERROR_INVALID_VALUE, "n_profiles must be 1 or n");
+    if (n_profiles == n && n_sectors > 1 && hstride < n) return fail(SUNSKY_ERROR_INVALID_VALUE, "horizon_stride < n");
+    if (grad_horizon && n_sectors > 1 && ghstride < n) return fail(SUNSKY_ERROR_INVALID_VALUE, "grad_horizon_stride < n");
+    return guarded([&] {
+        seq->require_irradiance_grad();   // the message names the missing call on any sequence
+        if (seq->irr_nphi % n_sectors != 0)
+            throw std::invalid_argument("n_sectors must be >= 1 and divide the irradiance tables' n_phi");
+        Launcher lc(seq, stream);
+        if (seq->irr_planes > 1 && d_stride < n) throw std::invalid_argument("d_stride < n");
+        SeqIrradiance S = seq->irr;
+        SeqIrrHorizon Z = {horizon, seq->d_irr_sun_cols, hstride, n_sectors, seq->irr_nphi / n_sectors,
+                           n_profiles == 1 ? 0 : 1, 0};
+        const bool spec = seq->variant == kSpectral;
+        if (grad_normal.x) {
+            void* args[] = {&lc.K, &S, &Z, (void*)&nrm.x, (void*)&nrm.y, (void*)&nrm.z, &active, &n, &d_out, &d_stride,
+                            (void*)&grad_normal.x, (void*)&grad_normal.y, (void*)&grad_normal.z};
+            lc.run(spec ? K_SEQUENCE_IRRADIANCE_HORIZON_VJP_NORMAL_SPEC : K_SEQUENCE_IRRADIANCE_HORIZON_VJP_NORMAL_RGB, n, args);
+        }
+        if (grad_horizon) {
+            void* args[] = {&lc.K, &S, &Z, (void*)&nrm.x, (void*)&nrm.y, (void*)&nrm.z, &active, &n, &d_out, &d_stride,
+                            &grad_horizon, &ghstride};
+            lc.run(spec ? K_SEQUENCE_IRRADIANCE_HORIZON_VJP_PROFILE_SPEC : K_SEQUENCE_IRRADIANCE_HORIZON_VJP_PROFILE_RGB, n, args);
+        }
+        if (!grad_weight) return;
+        const size_t cells = (size_t)seq->irr_nz * (size_t)seq->irr_nphi, entries = cells + (size_t)seq->count;
+        const SeqIrrGradShape shape = seq_irr_grad_shape(n, seq->irr_planes, cells, seq->count, seq->irr_grad_cap);
+        SeqIrrGrad G = seq->irr_grad;
+        G.dout = d_out;
+        G.dstride = d_stride;
+        G.slices = shape.slices;
+        G.slice_len = shape.slice_len;
+        Z.sun_cols = seq->d_irr_grad_cols;   // all K frames' columns
+        const size_t units = seq_irr_hz_grad_units(seq->irr_nz, Z.sector_len, n_sectors, seq->count);
+        const size_t passes = spec ? (size_t)(seq->irr_planes + kSeqIrrGradSpecPlanes - 1) / kSeqIrrGradSpecPlanes : 1;
+        {   // one workgroup per work item (slice, unit, pass), grid-stride over the items
+            void* args[] = {&lc.K, &S, &G, &Z, (void*)&nrm.x, (void*)&nrm.y, (void*)&nrm.z, &active, &n};
+            lc.run(K_SEQUENCE_IRRADIANCE_HORIZON_ADJOINT, (size_t)shape.slices * units * passes * kBlock, args);
         }
         SeqArgs A = seq->args();
         LambdaSet L = seq->irr_L;

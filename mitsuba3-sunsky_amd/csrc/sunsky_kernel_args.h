@@ -382,4 +382,19 @@ struct SeqIrrGrad {
 };
 static_assert(sizeof(SeqIrrGrad) == 56 && offsetof(SeqIrrGrad, omega) == 40, "SeqIrrGrad layout");
 
+// ---------------------------------------------------------------- ... under a horizon profile
+// sunsky_sequence_irradiance_horizon_vjp (sunsky_amd.h has the definition).  The kernels take the
+// forward's SeqIrrHorizon beside SeqIrrGrad; the adjoint's sun_cols are the columns of all K
+// frames, which prepare_irradiance_grad stages behind the fluxes.  The adjoint's work units are
+// sector-aware: per sector ceil(n_z sector_len / tile) tiles of its cells, then ceil(K / tile)
+// tiles of the suns; a tile has 256 lanes x 2 entries where a sector has at most
+// kSeqIrrHzGradNarrowCells cells, 256 x 4 otherwise.  The workspace row layout, the slices and
+// the fold are sunsky_sequence_irradiance_vjp's.
+constexpr int kSeqIrrHzGradNarrowCells = 512;
+inline size_t seq_irr_hz_grad_units(int nz, int sector_len, int sectors, int count) {
+    const size_t sector_cells = (size_t)nz * (size_t)sector_len;
+    const size_t tile = (size_t)kSeqIrrGradChunk * (sector_cells > (size_t)kSeqIrrHzGradNarrowCells ? 4 : 2);
+    return (size_t)sectors * ((sector_cells + tile - 1) / tile) + ((size_t)count + tile - 1) / tile;
+}
+
 }  // namespace sunsky

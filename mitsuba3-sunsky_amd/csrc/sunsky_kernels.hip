@@ -4322,3 +4322,4 @@ SS_BAKE(sunsky_bake_latlong_rgb_ref, sunsky_bake_latlong_spec_ref, false)
 #include "kernels/sequence_irradiance.h"        // frame sequences: irradiance on oriented receivers, with or without a horizon profile
 #include "kernels/sequence_irradiance_series.h" // frame sequences: the per-frame irradiance series
 #include "kernels/sequence_irradiance_grad.h"   // frame sequences: gradients of the irradiance (receiver normals, frame weights)
+#include "kernels/sequence_irradiance_horizon_grad.h"   // frame sequences: gradients of the irradiance under a horizon profile

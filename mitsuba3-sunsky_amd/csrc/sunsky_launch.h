@@ -111,6 +111,11 @@ std::string default_pack_path();   // SUNSKY_AMD_DATASET, else the pack beside t
     X(SEQUENCE_IRRADIANCE_VJP_NORMAL_SPEC, "sunsky_sequence_irradiance_vjp_normal_spec", 64, false, 2, FOUR) \
     X(SEQUENCE_IRRADIANCE_ADJOINT, "sunsky_sequence_irradiance_adjoint", kSeqIrrGradAdjointBlocksPerCu, false, 1, FOUR) \
     X(SEQUENCE_IRRADIANCE_GRAD_FOLD, "sunsky_sequence_irradiance_grad_fold", kSeqIrrGradFoldBlocksPerCu, false, 1, FOUR) \
+    X(SEQUENCE_IRRADIANCE_HORIZON_VJP_NORMAL_RGB, "sunsky_sequence_irradiance_horizon_vjp_normal_rgb", 64, false, 2, FOUR) \
+    X(SEQUENCE_IRRADIANCE_HORIZON_VJP_NORMAL_SPEC, "sunsky_sequence_irradiance_horizon_vjp_normal_spec", 64, false, 2, FOUR) \
+    X(SEQUENCE_IRRADIANCE_HORIZON_VJP_PROFILE_RGB, "sunsky_sequence_irradiance_horizon_vjp_profile_rgb", 64, false, 1, FOUR) \
+    X(SEQUENCE_IRRADIANCE_HORIZON_VJP_PROFILE_SPEC, "sunsky_sequence_irradiance_horizon_vjp_profile_spec", 64, false, 1, FOUR) \
+    X(SEQUENCE_IRRADIANCE_HORIZON_ADJOINT, "sunsky_sequence_irradiance_horizon_adjoint", kSeqIrrGradAdjointBlocksPerCu, false, 1, FOUR) \
     X(DEBUG_SUN_SEGMENTS, "sunsky_debug_sun_segments", 16, false, 1, FOUR)                         \
     X(EVAL_JVP_RGB, "sunsky_eval_jvp_rgb", 64, false, 1, PLAIN)                                    \
     X(EVAL_JVP_SPEC, "sunsky_eval_jvp_spec", 64, false, 1, PLAIN)                                  \

@@ -169,6 +169,8 @@ _SIGS = {
                                                     C.c_int, C.c_int, vp, C.c_size_t, vp]),
     "sunsky_sequence_prepare_irradiance_grad": (C.c_int, [vp]),
     "sunsky_sequence_irradiance_vjp": (C.c_int, [vp, Vec3In, vp, C.c_size_t, vp, C.c_size_t, Vec3Out, vp, vp]),
+    "sunsky_sequence_irradiance_horizon_vjp": (C.c_int, [vp, Vec3In, vp, C.c_int, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp,
+                                                         C.c_size_t, Vec3Out, vp, vp, C.c_size_t, vp]),
     "sunsky_direct_diffuse": (C.c_int, [vp, Vec3In, vp, vp, C.c_int, C.c_size_t, C.c_uint32, C.c_uint32,
                                         vp, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp]),
     "sunsky_direct_diffuse_rays": (C.c_int, [vp, Vec3In, C.c_uint32, C.c_uint32, C.c_size_t, Vec3Out, Vec3Out,

@@ -18,8 +18,8 @@ same caveats hold: the backward reads the sequence as it is when backward() runs
 update it (or call sequence_eval on it again) between a forward and its backward.
 
 sequence_irradiance(seq, normals, weights, ...) is seq.irradiance(normals) as a differentiable
-function of the receiver normals and the frame weights: the backward is seq.irradiance_vjp, with
-the same caveat.
+function of the receiver normals and the frame weights -- and, under a horizon profile
+(horizon=...), of the profile: the backward is seq.irradiance_vjp, with the same caveat.
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -86,11 +86,12 @@ class _SequenceEval(torch.autograd.Function):
 
 class _SequenceIrradiance(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, normals, seq, active, weights):
+    def forward(ctx, normals, seq, active, weights, horizon):
         nrm = normals.detach()
-        ctx.seq, ctx.active = seq, active
+        hz = None if horizon is None else horizon.detach()
+        ctx.seq, ctx.active, ctx.has_horizon = seq, active, hz is not None
         ctx.weights_device = weights.device if weights is not None else None
-        ctx.save_for_backward(nrm)
+        ctx.save_for_backward(*((nrm,) if hz is None else (nrm, hz)))
         if weights is not None:
             if seq.irradiance_args is None:
                 raise ValueError("sequence_irradiance needs seq.prepare_irradiance(...) first: it prepares again "
@@ -98,39 +99,49 @@ class _SequenceIrradiance(torch.autograd.Function):
             seq.update(weights=weights)
             n_z, n_phi, lam = seq.irradiance_args
             seq.prepare_irradiance(n_z, n_phi, lam)
-        if (ctx.needs_input_grad[0] or ctx.needs_input_grad[3]) and not seq.irradiance_grad_prepared:
+        if (ctx.needs_input_grad[0] or ctx.needs_input_grad[3] or ctx.needs_input_grad[4]) and not seq.irradiance_grad_prepared:
             seq.prepare_irradiance_grad()
-        return seq.irradiance(nrm, active)
+        return seq.irradiance(nrm, active) if hz is None else seq.irradiance(nrm, active, horizon=hz)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, d_out):
-        (nrm,) = ctx.saved_tensors
+        nrm, hz = ctx.saved_tensors if ctx.has_horizon else (ctx.saved_tensors[0], None)
         seq = ctx.seq
-        need_n, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[3]
+        need_n, need_w, need_h = ctx.needs_input_grad[0], ctx.needs_input_grad[3], ctx.needs_input_grad[4]
         grad = {"normals": torch.empty_like(nrm) if need_n else None,
                 "weights": torch.zeros(len(seq), dtype=torch.float32, device=seq.device) if need_w else None}
-        if need_n or need_w:
+        if hz is not None:
+            # a shared profile's gradient is the torch sum of the per-receiver columns (irradiance_vjp)
+            grad["horizon"] = torch.empty(hz.shape, dtype=torch.float32, device=seq.device) if need_h else None
+        if need_n or need_w or need_h:
             d = d_out if d_out.dim() == 2 and (d_out.shape[1] <= 1 or d_out.stride(1) == 1) else d_out.contiguous()
-            seq.irradiance_vjp(nrm, d, ctx.active, grad=grad)
+            seq.irradiance_vjp(nrm, d, ctx.active, grad=grad, horizon=hz)
         gw = grad["weights"]
-        return grad["normals"], None, None, None if gw is None else gw.to(ctx.weights_device)
+        return grad["normals"], None, None, None if gw is None else gw.to(ctx.weights_device), grad.get("horizon")
 
 
-def sequence_irradiance(seq, normals, weights=None, active=None):
-    """seq.irradiance(normals, active), differentiable in the normals and in the frame weights.
+def sequence_irradiance(seq, normals, weights=None, active=None, horizon=None):
+    """seq.irradiance(normals, active, horizon=horizon), differentiable in the normals, in the frame
+    weights and in the horizon profile.
 
     normals: (3, n) float32 tensor on the sequence's device.  weights: a (K,) float32 tensor (any
     device; its values are read on the host) or None to leave the sequence's weights as they are.
+    horizon: seq.irradiance's argument, a float32 tensor (H,), (H, 1) or (H, n) on the sequence's
+    device, or None for the open sky.
     With weights the forward calls seq.update(weights=...) and seq.prepare_irradiance with the
     arguments of the last prepare_irradiance; it returns bit for bit seq.irradiance's value.  The
-    backward is seq.irradiance_vjp: gradients for the normals and, on the weights' device, for the
-    weights.  Do not update the sequence between a forward and its backward."""
+    backward is seq.irradiance_vjp: gradients for the normals, on the weights' device for the
+    weights and, when it requires grad, for the horizon tensor in its own shape (a shared profile:
+    the per-receiver gradients summed by torch.sum).  Do not update the sequence between a forward
+    and its backward."""
     if not isinstance(normals, torch.Tensor) or normals.dtype != torch.float32 or normals.dim() != 2 or normals.shape[0] != 3:
         raise ValueError("normals must be a float32 tensor of shape (3, n)")
     if weights is not None and (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32):
         raise ValueError("weights must be a float32 tensor or None")
-    return _SequenceIrradiance.apply(normals, seq, active, weights)
+    if horizon is not None and (not isinstance(horizon, torch.Tensor) or horizon.dtype != torch.float32):
+        raise ValueError("horizon must be a float32 tensor or None")
+    return _SequenceIrradiance.apply(normals, seq, active, weights, horizon)
 
 
 def sequence_eval(seq, wi, weights=None, turbidity=None, sun_directions=None, wavelengths=None, active=None):

@@ -259,22 +259,44 @@ class SunskySequence:
         check(lib().sunsky_sequence_prepare_irradiance_grad(self._h))
         self.irradiance_grad_prepared = True
 
-    def irradiance_vjp(self, normals, d_out, active=None, grad=None):
+    def irradiance_vjp(self, normals, d_out, active=None, grad=None, horizon=None):
         """Reverse mode of irradiance(): with L = sum(d_out * irradiance(normals)), returns
         {"normals": (3, n) dL/dn, written, "weights": (K,) dL/dw_k, accumulated} as device tensors
         -- those of `grad` (an entry set to None is not computed) or new ones.  E is piecewise
         linear in n (the clamp's derivative is the strict step) and linear in w; every frame gets
         its weight gradient, a zero-weight one included.  Needs prepare_irradiance_grad.
-        Deterministic; calls on one sequence share a workspace, so order them across streams."""
+        Deterministic; calls on one sequence share a workspace, so order them across streams.
+
+        horizon: irradiance()'s argument; the gradients are then those of
+        irradiance(normals, horizon=horizon) (sunsky_sequence_irradiance_horizon_vjp) and the
+        result has a third entry, "horizon": dL/dh, written -- (H, n) for per-receiver profiles
+        (a row stride is allowed), the profile's own shape for a shared one (the per-receiver
+        columns of an internal (H, n) buffer summed by torch.sum).  In `grad`, a "horizon" entry
+        that is None or missing is not computed.  None: the unoccluded call, unchanged."""
+        if horizon is None and grad is not None and grad.get("horizon") is not None:
+            raise ValueError("grad['horizon'] needs a horizon")
         if self.device is None:
             # the library refuses, and says first which preparation is missing; it reads no pointer
             p = C.cast((C.c_float * 1)(), C.c_void_p)
-            check(lib().sunsky_sequence_irradiance_vjp(self._h, Vec3In(p, p, p), None, 1, p, 1,
-                                                       _capi.Vec3Out(None, None, None), None, None))
+            none = _capi.Vec3Out(None, None, None)
+            if horizon is None:
+                check(lib().sunsky_sequence_irradiance_vjp(self._h, Vec3In(p, p, p), None, 1, p, 1, none, None, None))
+            else:
+                self.irradiance_info()   # an unprepared sequence says so first
+                n = int(np.shape(normals)[-1])
+                _, sectors, profiles, _ = self._horizon(horizon, n)
+                if grad is not None:
+                    self._grad_horizon(grad.get("horizon"), tuple(horizon.shape), sectors, n,
+                                       self._shared_horizon(tuple(horizon.shape), n))
+                check(lib().sunsky_sequence_irradiance_horizon_vjp(self._h, Vec3In(p, p, p), p, sectors, 1, 1, None, 1, p, 1,
+                                                                   none, None, None, 1, None))
             raise ValueError("host-only sequence (over a host-only emitter) cannot launch kernels")
         nrm, vin = SunskyEmitter._vec_in(self, normals)
         n = nrm.shape[1]
         planes = self.irradiance_info()["n_planes"]
+        if horizon is not None:
+            hshape = tuple(horizon.shape) if isinstance(horizon, torch.Tensor) else None
+            horizon, sectors, profiles, hstride = self._horizon(horizon, n)
         mask = SunskyEmitter._mask(self, active, n)
         d_out = torch.as_tensor(d_out, dtype=torch.float32, device=self.device)
         if tuple(d_out.shape) != (planes, n):
@@ -286,6 +308,9 @@ class SunskySequence:
         if grad is None:
             grad = {"normals": torch.empty((3, n), dtype=torch.float32, device=self.device),
                     "weights": torch.zeros(count, dtype=torch.float32, device=self.device)}
+            if horizon is not None:
+                grad["horizon"] = torch.empty(hshape if self._shared_horizon(hshape, n) else (sectors, n),
+                                              dtype=torch.float32, device=self.device)
         for key, shape in shapes.items():
             g = grad.get(key)
             if g is not None and (not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or g.device != self.device
@@ -293,9 +318,43 @@ class SunskySequence:
                 raise ValueError(f"grad['{key}'] must be a contiguous float32 tensor of shape {shape} on {self.device}")
         gn, gw = grad.get("normals"), grad.get("weights")
         gout = _capi.Vec3Out(None, None, None) if gn is None else _capi.Vec3Out(*[gn[i].data_ptr() for i in range(3)])
-        check(lib().sunsky_sequence_irradiance_vjp(self._h, vin, _ptr(mask), n, _ptr(d_out), max(d_out.stride(0), n),
-                                                   gout, _ptr(gw), self._stream()))
+        if horizon is None:
+            check(lib().sunsky_sequence_irradiance_vjp(self._h, vin, _ptr(mask), n, _ptr(d_out), max(d_out.stride(0), n),
+                                                       gout, _ptr(gw), self._stream()))
+            return grad
+        gh = grad.get("horizon")
+        shared = self._shared_horizon(hshape, n)
+        self._grad_horizon(gh, hshape, sectors, n, shared)
+        # one column per receiver, also for a shared profile: its columns are summed below
+        buf = None if gh is None else torch.empty((sectors, n), dtype=torch.float32, device=self.device) if shared else gh
+        check(lib().sunsky_sequence_irradiance_horizon_vjp(self._h, vin, _ptr(horizon), sectors, profiles, hstride,
+                                                           _ptr(mask), n, _ptr(d_out), max(d_out.stride(0), n), gout,
+                                                           _ptr(gw), _ptr(buf), 0 if buf is None else max(buf.stride(0), n),
+                                                           self._stream()))
+        if gh is not None and shared and n:
+            gh.copy_(torch.sum(buf, dim=1).reshape(gh.shape))
+        grad["horizon"] = gh
         return grad
+
+    @staticmethod
+    def _shared_horizon(hshape, n):
+        """Whether a horizon of this shape is one profile for all n receivers: (H,) always, (H, 1)
+        with more than one receiver.  Decided from the shape given, not from n_profiles (which is 1
+        for a single receiver either way)."""
+        return len(hshape) == 1 or (hshape[1] == 1 and n > 1)
+
+    def _grad_horizon(self, gh, hshape, sectors, n, shared):
+        """A grad["horizon"] entry checked against the profile it belongs to: the profile's own
+        shape for a shared one, (H, n) with contiguous rows (a row stride is allowed) otherwise."""
+        if gh is None:
+            return
+        shape = hshape if shared else (sectors, n)
+        if (not isinstance(gh, torch.Tensor) or gh.dtype != torch.float32
+                or (self.device is not None and gh.device != self.device) or tuple(gh.shape) != shape
+                or (shared and not gh.is_contiguous())
+                or (not shared and (n > 1 and gh.stride(1) != 1 or sectors > 1 and gh.stride(0) < n))):
+            where = "" if self.device is None else f" on {self.device}"
+            raise ValueError(f"grad['horizon'] must be a float32 tensor of shape {shape}{where}, its rows contiguous")
 
     def irradiance_info(self):
         d = _capi.SequenceIrradianceDesc()

@@ -17,6 +17,9 @@ does an eval's transcendental work with no HBM traffic).  Not part of bench.py.
                 formulation a user writes from the read-back tables (see irradiance()).
   --irradiance-grad -- instead: sequence.irradiance_vjp beside sequence.irradiance and the torch
                 formulations of both gradients (see irradiance_grad()).
+  --irradiance-horizon-grad -- instead: sequence.irradiance_vjp(horizon=...) beside the open
+                irradiance_vjp, irradiance(horizon=...) and torch autograd through the masked
+                formulation (see irradiance_horizon_grad()).
   --irradiance-horizon -- instead: sequence.irradiance under a shared and a per-receiver horizon
                 profile beside the unoccluded call and the masked chunked torch formulation
                 (see irradiance_horizon()).
@@ -391,6 +394,137 @@ def irradiance_grad(ks, dev):
     print("sequence_bench irradiance-grad done")
 
 
+def irradiance_horizon_grad(ks, dev):
+    """--irradiance-horizon-grad: sequence.irradiance_vjp(horizon=...) on irradiance_horizon()'s workload
+    (n = 2^20 normals on the sphere, RGB, 64 x 256 cells, H = 32 sectors, sin of the elevation
+    uniform in [0, 0.5]) with a standard-normal cotangent: each gradient alone and all three, for a
+    shared and for per-receiver profiles.  Yardsticks of the same session, all existing code:
+    (a) irradiance_vjp (open) at the same n; (b) irradiance(horizon=); (c) what a user writes today
+    -- torch autograd through irradiance_horizon()'s masked chunked formulation, differentiated in
+    the normals and the profile, and for the weights irradiance_grad()'s per-frame table (here from
+    irradiance_frame_table) contracted with the masked cosines.  Prints the medians, the ratios and
+    the largest differences to (c).  The profile's gradient jumps where h n_z crosses an integer
+    (another row becomes the partly covered one), and torch forms i + 1 - h n_z with two roundings
+    where the kernel has one fma: the few entries within 1e-5 of such a crossing are counted and
+    left out of that difference."""
+    n, chunk, sectors = 1 << 20, 1 << 14, 32
+    g = torch.Generator(device=dev).manual_seed(3)
+    v = torch.randn((3, n), device=dev, generator=g)
+    nrm = (v / v.norm(dim=0, keepdim=True)).contiguous()
+    h_per = (0.5 * torch.rand((sectors, n), device=dev, generator=g)).contiguous()
+    h_shared = h_per[:, 0].contiguous()
+    d_out = torch.randn((3, n), device=dev, generator=g)
+    base = {"type": "sunsky", "sun_direction": [0.3, 0.4, 0.866], "turbidity": 3.0, "albedo": 0.2}
+    for k in ks:
+        dirs, turb, wts = frames(k)
+        seq = ss.SunskySequence(ss.load_dict(dict(base)), dirs, turb, wts)
+        seq.prepare_irradiance()
+        seq.prepare_irradiance_grad()
+        info = seq.irradiance_info()
+        nz, nphi, omega = info["n_z"], info["n_phi"], info["omega"]
+        length = nphi // sectors
+        z = (np.arange(nz) + 0.5) / nz
+        phi = (np.arange(nphi) + 0.5) * (2 * np.pi / nphi)
+        st = np.sqrt(1 - z * z)
+        D = np.stack([np.outer(st, np.cos(phi)).ravel(), np.outer(st, np.sin(phi)).ravel(), np.repeat(z, nphi)], 1)
+        D_t = torch.from_numpy(D.astype(np.float32)).to(dev)                                        # (cells, 3)
+        R_t = torch.from_numpy(omega * seq.irradiance_table("sky").reshape(3, -1)).to(dev)          # (3, cells)
+        S_t = torch.from_numpy(np.stack([seq.frame(i)["sun_dir_local"] for i in range(k)])).to(dev)  # (K, 3)
+        flux = seq.irradiance_table("sun_flux")                                                      # (3, K)
+        F_t = torch.from_numpy(wts[None, :] * flux).to(dev)
+        Fk_t = torch.from_numpy(np.ascontiguousarray(flux.T)).to(dev)                                # (K, 3)
+        T_t = torch.from_numpy(np.stack([omega * seq.irradiance_frame_table(i).reshape(3, -1) for i in range(k)])
+                               .astype(np.float32)).to(dev)                                         # (K, 3, cells)
+        sun_sector = torch.from_numpy(seq.irradiance_sun_columns().astype(np.int64) // length).to(dev)
+        top = torch.arange(1, nz + 1, device=dev, dtype=torch.float32)
+        out = torch.empty((3, n), device=dev)
+        gn, gw, gh = torch.empty((3, n), device=dev), torch.zeros(k, device=dev), torch.empty((sectors, n), device=dev)
+        gn_t, gw_t, gh_t = torch.empty((3, n), device=dev), torch.zeros(k, device=dev), torch.empty((sectors, n), device=dev)
+
+        def masks(nl, hc):
+            vis = (top[None, :, None] - hc[:, None, :] * nz).clamp(0, 1)                           # (c, nz, H)
+            vis = vis.repeat_interleave(length, dim=2).reshape(nl.shape[0], -1)                      # (c, cells)
+            return vis, S_t[None, :, 2] >= hc[:, sun_sector]                                         # (c, K)
+
+        def torch_normals_and_profile():
+            for a in range(0, n, chunk):
+                nl = nrm[:, a:a + chunk].t().detach().requires_grad_(True)
+                hc = h_per[:, a:a + chunk].t().detach().requires_grad_(True)
+                vis, seen = masks(nl, hc)
+                e = (torch.relu(nl @ D_t.t()) * vis) @ R_t.t() + (torch.relu(nl @ S_t.t()) * seen) @ F_t.t()
+                (e * d_out[:, a:a + chunk].t()).sum().backward()
+                gn_t[:, a:a + chunk] = nl.grad.t()
+                gh_t[:, a:a + chunk] = hc.grad.t()
+
+        def torch_weights():
+            gw_t.zero_()
+            with torch.no_grad():
+                for a in range(0, n, chunk):
+                    nl, dd = nrm[:, a:a + chunk].t(), d_out[:, a:a + chunk].t()
+                    vis, seen = masks(nl, h_per[:, a:a + chunk].t())
+                    ek = ((torch.relu(nl @ D_t.t()) * vis) @ T_t.reshape(3 * k, -1).t()).reshape(-1, k, 3)
+                    ek = ek + (torch.relu(nl @ S_t.t()) * seen)[:, :, None] * Fk_t[None]
+                    gw_t.add_((ek * dd[:, None, :]).sum((0, 2)))
+
+        def vjp(h, normals=False, weights=False, horizon=False):
+            def step():
+                if weights:
+                    gw.zero_()
+                buf = None if not horizon else gh if h.dim() == 2 else torch.empty(sectors, device=dev)
+                seq.irradiance_vjp(nrm, d_out, grad={"normals": gn if normals else None, "weights": gw if weights else None,
+                                                     "horizon": buf}, horizon=h)
+            return step
+
+        def open_weights():
+            gw.zero_()
+            seq.irradiance_vjp(nrm, d_out, grad={"normals": None, "weights": gw})
+
+        line = {"K": k, "n": n, "table": [nz, nphi], "sectors": sectors}
+        alls = {}
+
+        def timed(name, step):
+            t, ts = median_ms(step)
+            line[name + "_ms"] = round(t, 3)
+            alls[name + "_ms_all"] = [round(x, 3) for x in ts]
+            return t
+
+        t_on = timed("open_vjp_normals", lambda: seq.irradiance_vjp(nrm, d_out, grad={"normals": gn, "weights": None}))
+        t_ow = timed("open_vjp_weights", open_weights)
+        t_ob = timed("open_vjp_both", lambda: seq.irradiance_vjp(nrm, d_out, grad={"normals": gn, "weights": gw}))
+        t_f = timed("irradiance_horizon_per_receiver", lambda: seq.irradiance(nrm, out=out, horizon=h_per))
+        timed("irradiance_horizon_shared", lambda: seq.irradiance(nrm, out=out, horizon=h_shared))
+        t = {}
+        for kind, h in (("per_receiver", h_per), ("shared", h_shared)):
+            t[kind, "n"] = timed(f"{kind}_normals", vjp(h, normals=True))
+            t[kind, "w"] = timed(f"{kind}_weights", vjp(h, weights=True))
+            t[kind, "h"] = timed(f"{kind}_horizon", vjp(h, horizon=True))
+            t[kind, "nh"] = timed(f"{kind}_normals_and_horizon", vjp(h, normals=True, horizon=True))
+            t[kind, "all"] = timed(f"{kind}_all_three", vjp(h, normals=True, weights=True, horizon=True))
+            line[f"{kind}_normals_over_open"] = round(t[kind, "n"] / t_on, 3)
+            line[f"{kind}_weights_over_open"] = round(t[kind, "w"] / t_ow, 3)
+            line[f"{kind}_normals_and_horizon_over_normals"] = round(t[kind, "nh"] / t[kind, "n"], 3)
+            line[f"{kind}_all_three_over_open_both"] = round(t[kind, "all"] / t_ob, 3)
+            line[f"{kind}_all_three_over_forward"] = round(t[kind, "all"] / t_f, 3)
+        t_tn = timed("torch_normals_and_profile", torch_normals_and_profile)
+        t_tw = timed("torch_weights", torch_weights)
+        vjp(h_per, normals=True, weights=True, horizon=True)()
+        torch.cuda.synchronize()
+        line.update({"torch_over_normals_and_horizon": round(t_tn / t["per_receiver", "nh"], 2),
+                     "torch_over_weights": round(t_tw / t["per_receiver", "w"], 2),
+                     "torch_over_all_three": round((t_tn + t_tw) / t["per_receiver", "all"], 2),
+                     "max_diff_normals_of_max": float(((gn - gn_t).abs().max() / gn_t.abs().max()).item()),
+                     "max_diff_weights_of_max": float(((gw - gw_t).abs().max() / gw_t.abs().max()).item())})
+        x = h_per * nz
+        at_jump = (x - x.round()).abs() < 1e-5
+        dh = (gh - gh_t).abs() / gh_t.abs().max()
+        line.update({"max_diff_horizon_of_max": float(dh[~at_jump].max().item()),
+                     "horizon_entries_at_a_row_crossing": int(at_jump.sum().item()),
+                     "max_diff_horizon_of_max_at_a_row_crossing": float(dh[at_jump].max().item()) if bool(at_jump.any()) else 0.0})
+        line.update(alls)
+        print(json.dumps(line), flush=True)
+    print("sequence_bench irradiance-horizon-grad done")
+
+
 def irradiance_series(ks, dev):
     """--irradiance-series: every frame's own irradiance on 2^20 receivers (RGB, normals uniform on
     the sphere, 64 x 256 cells) in one call per frame sub-range, open and under per-receiver
@@ -483,13 +617,15 @@ def irradiance_series(ks, dev):
 
 def main():
     flags = ("--sampling", "--grad", "--no-loop", "--irradiance", "--irradiance-grad", "--irradiance-horizon",
-             "--irradiance-series")
+             "--irradiance-series", "--irradiance-horizon-grad")
     args = [a for a in sys.argv[1:] if a not in flags]
     ks = [int(a) for a in args] or [24, 365]
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     if "--sampling" in sys.argv[1:]:
         return sampling(ks, dev)
+    if "--irradiance-horizon-grad" in sys.argv[1:]:
+        return irradiance_horizon_grad(ks, dev)
     if "--irradiance-series" in sys.argv[1:]:
         return irradiance_series(ks, dev)
     if "--irradiance" in sys.argv[1:]:
