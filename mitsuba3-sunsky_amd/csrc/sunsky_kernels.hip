@@ -74,7 +74,8 @@ __device__ __forceinline__ float safe_sqrt_sel(float x) {
 // asin on [0, sqrt(0.5)]: the half chord h = |wo -/+ n| / 2 of unit_angle never
 // exceeds sqrt(2) / 2, so one odd minimax polynomial x + x^3 P(x^2) (degree 7 in
 // x^2; fitted by tools/fit_asin.py) replaces libm's two-range asin (select,
-// sqrt, polynomial, fix-up).  Max error 0.71 ulp over [0, 0.7075] in fp32 (FAST only).
+// sqrt, polynomial, fix-up).  Max error 0.71 ulp over [0, 0.7075] in fp32 (FAST only; 0.708 over
+// every float of it on gfx950, tests/test_gpu_device_math.py).
 __device__ __forceinline__ float asin_half_chord(float x) {
     const float t = x * x;
     float p = 0.10696864128112793f;
@@ -93,14 +94,16 @@ __device__ __forceinline__ float asin_half_chord(float x) {
 // pi/2 - 2 asin(sqrt((1 - z) / 2)) (argument <= sqrt(1/2); 0.5 - 0.5 z exact there).  One
 // polynomial on a selected argument instead of libm's two-range acosf.  asin z does not
 // cancel near the horizon, where pi/2 - acos z loses ~1e-7 absolute (measured 2x over
-// the sun-disc bound at 0.1 degrees with a fast acos).
+// the sun-disc bound at 0.1 degrees with a fast acos).  Against asin z over every float of [0, 1]
+// on gfx950: 0.71 ulp up to the switch, 2.2 ulp (1.8e-7) above it (tests/test_gpu_device_math.py).
 __device__ __forceinline__ float elevation_fast(float z) {
     const bool big = z > 0.70710678f;
     const float p = asin_half_chord(big ? fast_sqrt(fmaf(-0.5f, z, 0.5f)) : z);
     return big ? fmaf(-2.f, p, kHalfPi) : p;
 }
 
-// atan on [0, 1]: t + t^3 P(t^2), degree 7 in t^2 (tools/fit_atan.py; 1.07 ulp).
+// atan on [0, 1]: t + t^3 P(t^2), degree 7 in t^2 (tools/fit_atan.py; 1.08 ulp over every float of
+// [0, 1] on gfx950, tests/test_gpu_device_math.py; the fit's 4M samples showed 1.07).
 __device__ __forceinline__ float atan_unit(float t) {
     const float u = t * t;
     float p = 0.0025049929972738028f;
@@ -116,7 +119,8 @@ __device__ __forceinline__ float atan_unit(float t) {
 
 // FAST atan2 for the TGMM pdf's azimuth: octant reduction t = min / max with
 // v_rcp_f32, atan_unit, then pi/2 - a and pi - a fix-ups (max error 4.4 ulp,
-// 3.5e-7 absolute over the circle; tools/fit_atan.py).  atan2(0, 0) returns a
+// 3.5e-7 absolute over the circle; tools/fit_atan.py; 3.0 ulp, 3.1e-7 measured on gfx950,
+// tests/test_gpu_device_math.py).  atan2(0, 0) returns a
 // finite value: the callers mask sin(theta) = 0 directions out (sunsky.cpp:717).
 __device__ __forceinline__ float atan2_fast(float y, float x) {
     const float ax = fabsf(x), ay = fabsf(y);
@@ -144,8 +148,10 @@ __device__ __forceinline__ float div_by_rcp(float a, float b, float rb) {
 
 // (lambda - 320) / 40, the per-lane wavelength's channel coordinate (sunsky.cpp:326), as
 // div_by_rcp by the correctly rounded 1/40: equal to the IEEE quotient for every float
-// (checked exhaustively on the host for |a| in [2^-100, 2^100]; below, the division
-// itself; inf / NaN give an invalid coordinate either way), without the division sequence.
+// but the two infinities (checked for all 2^32 lambda on the GPU,
+// tests/test_gpu_device_math.py::test_wavelength_node_is_the_ieee_quotient_for_every_float;
+// below |a| = 2^-100 it is the division itself; +-inf give NaN where the division gives +-inf,
+// an invalid coordinate either way), without the division sequence.
 __device__ __forceinline__ float wavelength_node(float lambda) {
     return div_by_rcp(lambda - kWavelength0, kWavelengthStep, 1.f / kWavelengthStep);
 }
@@ -167,8 +173,10 @@ __device__ __forceinline__ float div_exact(float a, float b, float rb) {
 
 // FAST sincos for the sampling transforms (sphdir, the concentric disk): one
 // Cody-Waite reduction by pi/2 (two fp32 constants, fma), then sin r = r + r^3 S(r^2)
-// and cos r = 1 - r^2/2 + r^4 C(r^2) on [-pi/4, pi/4] (tools/fit_sincos.py: max
-// 1.5 ulp, 9.2e-8 absolute for |x| <= 8 pi) and the quadrant swap / signs.  The
+// and cos r = 1 - r^2/2 + r^4 C(r^2) on [-pi/4, pi/4] (tools/fit_sincos.py) and the quadrant
+// swap / signs.  Over every float with |x| <= 8 pi on gfx950: 9.3e-8 absolute, 1.56 ulp where
+// |value| > 1e-3, 5.8 ulp next to the zeros (tests/test_gpu_device_math.py; the fit's 8M samples
+// showed 9.2e-8 and 1.5).  sincos_fast(-0) is (+0, 1).  The
 // arguments here stay within a few pi, far from where the two-constant reduction
 // loses bits.
 __device__ __forceinline__ void sincos_fast(float x, float* s, float* c) {
@@ -201,7 +209,8 @@ __device__ __forceinline__ void sincos_sel(float x, float* s, float* c) {
 // FAST erfinv: Giles' single-precision polynomials (erfinvf_, sunsky_math.h) with
 // w = -log(1 - x^2) from v_log_f32 (log2) times ln 2 instead of libm's logf.  The
 // result's relative sensitivity to w is ~0.3 dw, so the hardware log's few-ulp
-// error stays at the 1e-7 level.
+// error stays at the 1e-7 level (over every float of [-(1 - 2^-23), 1 - 2^-23] on gfx950: at most
+// 2 ulp from erfinvf_, 3.7 ulp from erfinv; tests/test_gpu_device_math.py).
 __device__ __forceinline__ float erfinv_fast(float x) {
     float w = -0.693147180559945309f * __builtin_amdgcn_logf(fmaf(x, -x, 1.f)), p;
     if (w < 5.f) {
@@ -391,7 +400,7 @@ __device__ __forceinline__ const SunskyKArgs& opaque_kargs(const SunskyKArgs& K)
 // (tests/test_gpu_sampler_disc_literal.py).
 struct SunDisc64 {
     int pos;     // render_sun's segment: the reference's fp32 decision (sun_segment_index)
-    double x;    // elevation - pi/2 (pos / 45)^3: the fp32 elevation (elevation_fast, 0.7 ulp;
+    double x;    // elevation - pi/2 (pos / 45)^3: the fp32 elevation (elevation_fast, 0.71 ulp to 45 degrees, 2.2 above;
                  // x enters the polynomial smoothly), the segment start in fp64
     double cpsi; // compute_cos_psi from the chord v = wo - n formed in fp64 (exact)
 };

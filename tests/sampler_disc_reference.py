@@ -46,10 +46,14 @@ t = o64t.eval / pdf on a disc lane,
         with powif_ products and separate adds) has one more in the limb darkening: N = 23 is
         used for both.
   dx: x = elevation_fast(z) - kHalfPi (frac frac frac), frac = pos (1 / 45), in fp32 against the
-      fp64 x above on the same fp32 z: elevation_fast is within 0.7 ulp of the elevation E
-      (its comment; an ulp is at most 2^-23 E); the segment start B = pi/2 (pos / 45)^3 carries
-      the rounding of 1 / 45, three products and kHalfPi and its product, 6 u B; the subtraction
-      (or the fma's one rounding) u |x|.  dx = 0.7 2^-23 E + 6 u B + u |x|.
+      fp64 x above on the same fp32 z: elevation_fast is within e ulp of the elevation E (an ulp
+      is at most 2^-23 E), e = 0.71 up to its switch z = 0.70710678 (asin_half_chord's stated
+      figure, 0.708 over every float on the GPU) and 4.11 above it, where it is pi/2 - 2 asin of
+      a square root (the operation-count bound of tests/test_gpu_device_math.py; 2.16 measured:
+      the 0.7 this term used to carry for every z does not hold there); the segment start
+      B = pi/2 (pos / 45)^3 carries the rounding of 1 / 45, three products and kHalfPi and its
+      product, 6 u B; the subtraction (or the fma's one rounding) u |x|.
+      dx = e 2^-23 E + 6 u B + u |x|.
   dc: cos psi = v_sqrt_f32(max(c2, 0)) with c2 the fp32 rounding of an fp64 expression of the
       exact chord (the comment in add_sun_terms): relative u on c2 is u / 2 on c, the 1 ulp
       square root 2^-23 c.  The fp64 expression itself (cpsi_inv_hi + cpsi_inv_lo carries
@@ -76,6 +80,7 @@ import oracle as O
 
 U = 2.0 ** -24
 RTOL = 1e-5
+ELEVATION_SWITCH = math.asin(float(np.float32(0.70710678)))   # elevation_fast changes form above this elevation
 N_RGB = 15
 N_SPEC = 23
 SPEC_TO_RGB_SUN_CONV = 467.069280386
@@ -293,7 +298,8 @@ class LocalDisc:
         """(n, C): the admissible |w - ref| of a FAST sampler's weight on the disc lanes, for the
         reference weights ref (n, C) and the density pdf, (n,) or (n, C), the weights were divided by."""
         t = terms
-        dx = 0.7 * 2.0 ** -23 * np.abs(t.E) + 6 * U * t.B + U * np.abs(t.x)
+        e = np.where(t.E > ELEVATION_SWITCH, 4.11, 0.71)   # elevation_fast below / above z = 0.70710678
+        dx = e * 2.0 ** -23 * np.abs(t.E) + 6 * U * t.B + U * np.abs(t.x)
         dc = 1.25 * 2.0 ** -23 * t.c + np.minimum(2.0 ** -47 / np.maximum(t.c, 1e-300), 2.0 ** -23)
         err = gamma_n(self.n_rounds) * t.A + np.abs(t.dSdx) * dx[:, None] + np.abs(t.dSdc) * dc[:, None]
         if self.spectral:

@@ -7,7 +7,7 @@ oracle's own worst ratio on the same samples against the same restatement at the
 directions (ray_figures).  The two frame-independent invariants (|q . d| and ||q| - |r||, q the
 ray's offset on its disk) are held to twice the fp32 oracle's own worst value likewise.  The
 factor 2 covers what a kernel may differ in from the fp32 reference and still be as accurate:
-sincos_fast's documented 1.5 ulp / 9.2e-8 absolute, one v_rcp ulp on phi, another libm."""
+sincos_fast's 1.56 ulp / 9.3e-8 absolute (tests/test_gpu_device_math.py), one v_rcp ulp on phi, another libm."""
 import functools
 import hashlib
 import os
